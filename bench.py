@@ -6,11 +6,18 @@ One step = one full EM iteration: M-step sufficient statistics + fused
 RCCL all-reduce + covariance/constants finalize + E-step + likelihood
 reduce — nothing skipped.
 
-Reports BOTH precisions per run: the headline JSON
-line is the --dtype mode (default bf16, sanctioned by BASELINE config 2);
-its "modes" field carries the exact-fp32 measurement (fp32 E-step + fp32
-MFMA moments — the reference's precision throughout, gaussian_kernel.cu)
-taken back-to-back in the same process on the same data.
+A plain run measures only the headline: the --dtype mode (default bf16,
+sanctioned by BASELINE config 2). With --full the run reports BOTH
+precisions: the "modes" field of the JSON line then
+also carries the other precision's measurement (for the bf16 headline
+that is exact fp32: fp32 E-step + fp32 MFMA moments — the reference's
+precision throughout, gaussian_kernel.cu) taken back-to-back in the same
+process on the same data.
+
+--dump-outputs DIR writes what the last timed iteration of the headline
+mode left behind (model parameters, likelihood, a fixed seeded sample of
+the posteriors) as DIR/<name>.npy, so two builds can be compared output
+for output: the inputs depend only on the arguments.
 
 Run directly (1 GPU) or under torch.distributed.run with one rank per GPU:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -32,10 +39,54 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # all dumped arrays together (< 64 MB)
+DUMP_SAMPLE_EVENTS = 32768     # posterior columns kept (seeded sample)
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(engine, k: int, out_dir: str) -> None:
+    """Write the state the last em_iteration(k) produced — what a caller
+    of the engine reads back after a step — as float32 .npy files: the
+    model parameters (means in data coordinates), the reduced
+    log-likelihood and the normalized posteriors of this rank's shard,
+    the latter restricted to a fixed seeded sample of event columns
+    ([K, N] itself is 256 MB at the flagship shape)."""
+    st = engine.state.shrink(k)
+    arrays = {
+        "N": st.N,
+        "pi": st.pi,
+        "means": st.means + engine.center.unsqueeze(0),
+        "R": st.R,
+        "constant": st.constant,
+        "likelihood": engine._lik_dev,
+    }
+    out = {name: t.detach().to("cpu", torch.float32).numpy().copy()
+           for name, t in arrays.items()}
+    used = sum(a.nbytes for a in out.values())
+    room = (DUMP_BUDGET_BYTES - used) // (4 * k)
+    if room < 1:
+        raise SystemExit("--dump-outputs: model parameters alone exceed "
+                         "the dump budget at this K/D")
+    n = engine.n_shard
+    m = int(min(n, DUMP_SAMPLE_EVENTS, room))
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED)
+                  .choice(n, size=m, replace=False))
+    cols = torch.from_numpy(idx).to(engine.device)
+    out["posteriors_sample"] = (
+        engine.posteriors(k).index_select(1, cols)
+        .to("cpu", torch.float32).numpy().copy())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def time_mode(dtype: str, data, device: str, k: int, steps: int,
-              warmup: int, world: int, profile: bool) -> dict:
+              warmup: int, world: int, profile: bool,
+              dump_dir: str | None = None) -> dict:
     """Build an engine in the given precision and time `steps` iterations
-    bracketed by barrier + synchronize on both sides; MAX over ranks."""
+    bracketed by barrier + synchronize on both sides; MAX over ranks.
+    With `dump_dir` rank 0 writes the last step's outputs there, after
+    the clock has stopped."""
     from cuda_gmm_mpi_amd.engine import build_engine
     from cuda_gmm_mpi_amd.parallel import dist as pdist
     from cuda_gmm_mpi_amd.utils.config import GmmConfig
@@ -75,6 +126,8 @@ def time_mode(dtype: str, data, device: str, k: int, steps: int,
         elapsed = float(t.item())
     report = engine.profile.report(0, 0) if profile else None
     likelihood = float(engine._lik_dev.item())  # sanity: finite math ran
+    if dump_dir and pdist.rank() == 0:
+        dump_outputs(engine, k, dump_dir)
     del engine
     if has_gpu:
         torch.cuda.empty_cache()
@@ -96,10 +149,16 @@ def main() -> int:
     p.add_argument("--clusters", type=int, default=64)
     p.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     p.add_argument("--modes", choices=["both", "single"], default=None,
-                   help="'both' (GPU default) also measures the other "
-                        "precision back-to-back and reports it in the "
-                        "'modes' field of the JSON line")
+                   help="'both' (the --full default on a GPU) also "
+                        "measures the other precision back-to-back and "
+                        "reports it in the 'modes' field of the JSON line")
     p.add_argument("--profile", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (today: the other precision, see --modes)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "outputs of the headline mode as DIR/<name>.npy")
     args = p.parse_args()
 
     from cuda_gmm_mpi_amd.parallel import dist as pdist
@@ -114,7 +173,7 @@ def main() -> int:
     steps = args.steps if args.steps is not None else (300 if has_gpu else 10)
     warmup = (args.warmup if args.warmup is not None
               else (20 if has_gpu else 2))
-    modes = args.modes or ("both" if has_gpu else "single")
+    modes = args.modes or ("both" if (args.full and has_gpu) else "single")
     n_total = events_per_gpu * world
     k, d = args.clusters, args.dims
 
@@ -124,7 +183,7 @@ def main() -> int:
 
     main_dtype = args.dtype if has_gpu else "fp32"
     res = time_mode(main_dtype, data, device, k, steps, warmup, world,
-                    args.profile)
+                    args.profile, args.dump_outputs)
     extra = {}
     if modes == "both" and has_gpu:
         other = "fp32" if main_dtype == "bf16" else "bf16"
@@ -165,7 +224,8 @@ def main() -> int:
                 "note": ("bf16 E-step data reads, fp32 accumulate; "
                          "split-precision bf16x3 M-step moments; fp32 "
                          "constants/finalize (BASELINE config 2/3); "
-                         "'modes.fp32' is the exact-fp32 measurement"
+                         "with --full 'modes.fp32' is the exact-fp32 "
+                         "measurement"
                          if main_dtype == "bf16" else
                          "exact fp32 E-step and M-step (reference "
                          "precision)"),

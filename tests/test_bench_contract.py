@@ -45,11 +45,69 @@ def test_bench_single_process_cpu():
     assert d["config"]["n_events"] == 3000
 
 
+@pytest.mark.timeout(600)
+def test_bench_full_and_dump_outputs_cpu(tmp_path):
+    """--full keeps the one-line contract, and --dump-outputs writes the
+    last step's outputs as small float .npy files that repeat from run
+    to run (same arguments -> same inputs -> same outputs)."""
+    import numpy as np
+    args = ["--steps", "2", "--warmup", "1", "--events-per-gpu", "3000",
+            "--clusters", "5", "--dims", "4"]
+    dumps = []
+    for name, extra in (("a", ["--full"]), ("b", [])):
+        out_dir = tmp_path / name
+        d = run_bench(args + extra + ["--dump-outputs", str(out_dir)])
+        check_contract(d, 1)
+        assert d["steps"] == 2 and d["dtype"] in d["modes"]
+        dumps.append({p.stem: np.load(p) for p in out_dir.glob("*.npy")})
+    a, b = dumps
+    assert set(a) == set(b) == {"N", "pi", "means", "R", "constant",
+                                "likelihood", "posteriors_sample"}
+    assert a["means"].shape == (5, 4) and a["R"].shape == (5, 4, 4)
+    assert a["posteriors_sample"].shape == (5, 3000)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.all(np.isfinite(a[name])), name
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6,
+                                   err_msg=name)
+    np.testing.assert_allclose(a["posteriors_sample"].sum(axis=0), 1.0,
+                               atol=1e-4)
+    np.testing.assert_allclose(a["N"].sum(), 3000.0, rtol=1e-4)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_bench_full_and_dump_outputs_gpu(tmp_path):
+    """On the GPU --full adds the other precision to `modes`; the dump
+    holds the headline (bf16) mode's last step, posteriors sampled."""
+    import numpy as np
+    d = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "2",
+                   "--events-per-gpu", "100000", "--full",
+                   "--dump-outputs", str(tmp_path)], timeout=280)
+    check_contract(d, 1)
+    assert d["dtype"] == "bf16" and set(d["modes"]) == {"bf16", "fp32"}
+    assert d["modes"]["bf16"]["ms_per_step"] == d["ms_per_step"]
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == {"N", "pi", "means", "R", "constant", "likelihood",
+                        "posteriors_sample"}
+    assert got["R"].shape == (64, 24, 24)
+    assert got["posteriors_sample"].shape == (64, 32768)
+    for name, a in got.items():
+        assert a.dtype == np.float32 and np.all(np.isfinite(a)), name
+    np.testing.assert_allclose(got["posteriors_sample"].sum(axis=0), 1.0,
+                               atol=1e-3)
+    np.testing.assert_allclose(got["pi"].sum(), 1.0, atol=1e-3)
+
+
 @pytest.mark.timeout(900)
 def test_bench_torchrun_world2_cpu():
     """The driver's exact launch form, world 2 on gloo."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
+    # a CPU test wherever it runs: on a one-GPU box both ranks would
+    # otherwise land on that GPU and RCCL refuses ("Duplicate GPU")
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
