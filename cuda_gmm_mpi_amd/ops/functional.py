@@ -350,6 +350,12 @@ def split_bf16_planes(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return hi.contiguous(), lo.contiguous()
 
 
+# default chunk count of the pair-column bf16x3 moments kernel: one block per
+# 64 clusters and chunk, so 256 chunks = one block per CU at K <= 64 (sweep
+# 128..2048 in profiles/LADDER.md R33: 256 fastest, 512 +10%, 128 +70%)
+PAIR_NCHUNK = 256
+
+
 def mstep_moments(x: torch.Tensor, w: torch.Tensor,
                   nchunk: int | None = None,
                   precision: str = "fp32",
@@ -370,11 +376,18 @@ def mstep_moments(x: torch.Tensor, w: torch.Tensor,
     p = d * (d + 1) // 2
     if x.is_cuda and d <= 31:
         tiles = (n + 127) // 128
+        # bf16x3 runs the pair-column GEMM kernel; GMM_MOMENTS_B16=legacy
+        # selects the per-cluster A = w.z kernel (same-build A/B)
+        pair = (precision == "bf16x3"
+                and os.environ.get("GMM_MOMENTS_B16", "pair") != "legacy")
         if nchunk is None:
             # enough chunk-parallelism to fill 8 XCDs x 32 CUs, capped so
             # the partial buffer stays <= 64 MB (measured sweeps: bf16x3
             # fastest at ~256 chunks, fp32 at ~512, K=64 N=1M)
             target = 256 if precision == "bf16x3" else 512
+            if pair:
+                # one block per 64 clusters and chunk (not one per 8)
+                target = PAIR_NCHUNK
             nchunk = max(1, min(target, (64 << 20) // (4 * k * pp)))
         nchunk = int(min(nchunk, tiles))
         partials = torch.empty((nchunk, k, pp), dtype=torch.float32,
@@ -384,8 +397,9 @@ def mstep_moments(x: torch.Tensor, w: torch.Tensor,
         if precision == "bf16x3":
             if x_split is None:
                 x_split = split_bf16_planes(x)
-            hip_ext().mstep_moments_b16(x_split[0], x_split[1], w, lse_t,
-                                        partials)
+            kern = (hip_ext().mstep_moments_pair_b16 if pair
+                    else hip_ext().mstep_moments_b16)
+            kern(x_split[0], x_split[1], w, lse_t, partials)
         else:
             hip_ext().mstep_moments(x, w, lse_t, partials)
         out = torch.empty((k, pp), dtype=torch.float32, device=x.device)

@@ -307,6 +307,79 @@ void mstep_moments_b16(torch::Tensor xhi, torch::Tensor xlo,
   HIP_CHECK(hipGetLastError());
 }
 
+template <int TPW, int NCT>
+void launch_moments_pair(int nchunk, const torch::Tensor& xhi,
+                         const torch::Tensor& xlo, const torch::Tensor& w,
+                         const float* lse, torch::Tensor& partials, int d,
+                         int k, int64_t n) {
+  constexpr size_t lds = 2 * MP_BUF_BYTES(NCT);  // double-buffered, > 64 KB
+  dim3 grid((k + 16 * NCT - 1) / (16 * NCT), nchunk);
+  HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(
+          &gmm::mstep_moments_pair_b16_kernel<TPW, NCT>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((gmm::mstep_moments_pair_b16_kernel<TPW, NCT>), grid,
+                     dim3(MP_NT), lds, stream(),
+                     reinterpret_cast<const __hip_bfloat16*>(xhi.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(xlo.data_ptr()),
+                     w.data_ptr<float>(), lse, partials.data_ptr<float>(), d,
+                     k, n, nchunk);
+}
+
+void mstep_moments_pair_b16(torch::Tensor xhi, torch::Tensor xlo,
+                            torch::Tensor w, torch::Tensor lse,
+                            torch::Tensor partials) {
+  TORCH_CHECK(xhi.is_cuda() && xhi.is_contiguous() && xlo.is_cuda() &&
+                  xlo.is_contiguous() &&
+                  xhi.scalar_type() == torch::kBFloat16 &&
+                  xlo.scalar_type() == torch::kBFloat16 &&
+                  xlo.sizes() == xhi.sizes() && xhi.dim() == 2,
+              "xhi/xlo must be contiguous bf16 [D, N] planes");
+  check_f32(w, "w");
+  check_f32(partials, "partials");
+  const int d = (int)xhi.size(0);
+  const int64_t n = xhi.size(1);
+  const int k = (int)w.size(0);
+  TORCH_CHECK(partials.dim() == 3 && partials.size(0) >= 1,
+              "partials must be [nchunk, K, Dp*(Dp+1)/2]");
+  const int nchunk = (int)partials.size(0);
+  const int dp = d + 1;
+  const int pp = dp * (dp + 1) / 2;
+  TORCH_CHECK(d >= 1 && d <= 31, "mstep_moments_pair_b16 needs 1 <= D <= 31");
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == n && k >= 1 && n >= 1,
+              "w must be [K, N]");
+  TORCH_CHECK(partials.size(1) == k && partials.size(2) == pp,
+              "partials must be [nchunk, K, Dp*(Dp+1)/2]");
+  TORCH_CHECK(nchunk <= 65535, "nchunk must fit gridDim.y");
+  const float* lp = lse_ptr(lse, n);
+  // 16-column pair tiles over 8 waves: tiles per wave (<= 5 at D <= 31);
+  // 64 clusters per block up to 3 tiles per wave, 32 above
+  const int tpw = ((pp + 15) / 16 + 7) / 8;
+  switch (tpw) {
+    case 1: launch_moments_pair<1, 4>(nchunk, xhi, xlo, w, lp, partials, d, k, n); break;
+    case 2: launch_moments_pair<2, 4>(nchunk, xhi, xlo, w, lp, partials, d, k, n); break;
+    case 3: launch_moments_pair<3, 4>(nchunk, xhi, xlo, w, lp, partials, d, k, n); break;
+    case 4: launch_moments_pair<4, 2>(nchunk, xhi, xlo, w, lp, partials, d, k, n); break;
+    default: launch_moments_pair<5, 2>(nchunk, xhi, xlo, w, lp, partials, d, k, n); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void exp_sub_lse(torch::Tensor logw, torch::Tensor lse, torch::Tensor out) {
+  check_f32(logw, "logw");
+  check_f32(out, "out");
+  TORCH_CHECK(logw.dim() == 2 && out.sizes() == logw.sizes(),
+              "logw/out must be [K, N]");
+  const int k = (int)logw.size(0);
+  const int64_t n = logw.size(1);
+  const float* lp = lse_ptr(lse, n);
+  TORCH_CHECK(lp != nullptr, "lse must be [N]");
+  hipLaunchKernelGGL(gmm::exp_sub_lse_kernel, dim3(grid_x_for((int64_t)k * n)),
+                     dim3(kNT), 0, stream(), logw.data_ptr<float>(), lp,
+                     out.data_ptr<float>(), k, n);
+  HIP_CHECK(hipGetLastError());
+}
+
 void estep_fused(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
                  torch::Tensor w_out, torch::Tensor lse_out,
                  torch::Tensor partial) {
@@ -738,6 +811,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "split-precision bf16x3 augmented moments");
   m.def("mstep_moments", &mstep_moments,
         "fused augmented moments [S|mean_num|N] via f32 MFMA");
+  m.def("mstep_moments_pair_b16", &mstep_moments_pair_b16,
+        "split-precision bf16x3 moments as one W.P GEMM over pair columns");
+  m.def("exp_sub_lse", &exp_sub_lse,
+        "out[c, e] = __expf(logw[c, e] - lse[e]) (moments staging twin)");
   m.def("reduce_chunks", &reduce_chunks,
         "deterministic chunk-partials reduction out[j] = sum_i in[i][j]");
   m.def("reduce_scalar", &reduce_scalar,

@@ -19,6 +19,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #define WAVE 64
 #define NT 256  // threads per workgroup (4 waves)
@@ -1165,6 +1166,322 @@ mstep_moments_b16_kernel(const __hip_bfloat16* __restrict__ xhi,
     if (gi < dp && gj <= gi)
       out[gi * (gi + 1) / 2 + gj] = accA[r] + accB[r];
   }
+}
+
+// ---------------------------------------------------------------------------
+// Split-precision (bf16x3) moments regrouped as ONE GEMM over pair columns:
+//   T_c[i,j] = sum_e w_ce (z_i z_j)_e   ->   C[K x PP] = W[K x N] . P[N x PP]
+// with column p = i(i+1)/2 + j (j <= i) — exactly the packed row layout of
+// partials[chunk][c][.], so there is no triangle masking and no wasted upper
+// half. The per-(cluster, dim, event) rebuild + hi/lo split of A = w.z that
+// bounds mstep_moments_b16_kernel is gone:
+//   A[row=cluster][kk=event] = w        split ONCE by the staging thread
+//   B[kk=event][col=pair]    = z_i z_j  built + split in registers, shared
+//                                       by all 64 clusters of the block
+// One block owns 16*NCT clusters (NCT 16-row A tiles; 64 clusters up to
+// D = 26) and ALL pair tiles of its event chunk, so w (the 256 MB operand)
+// is read once. Pair tiles are 16 columns wide on v_mfma_f32_16x16x32_bf16;
+// wave v of 8 owns tiles v, v+8, ... (TPW per wave, statically indexed
+// accumulators: 8*TPW*NCT registers). D >= 27 (TPW 4-5) runs NCT = 2 to
+// stay inside the register file without spilling.
+// LDS per buffer: z [32][MP_ZROW] f32 (hi+lo rebuilt once at staging),
+// w hi / w lo [16*NCT][MP_WROW] bf16 — an A fragment is one ds_read_b128.
+// ---------------------------------------------------------------------------
+#define MP_BK 128
+#define MP_NT 512
+#define MP_WROW (MP_BK + 8)   // bf16 per staged w row
+#define MP_ZROW (MP_BK + 4)   // f32 per staged z row
+// bytes per LDS buffer for NCT 16-row cluster tiles per block
+#define MP_BUF_BYTES(NCT) (32 * MP_ZROW * 4 + 2 * 16 * (NCT) * MP_WROW * 2)
+
+template <int TPW, int NCT>
+__global__ void __launch_bounds__(MP_NT)
+mstep_moments_pair_b16_kernel(const __hip_bfloat16* __restrict__ xhi,
+                              const __hip_bfloat16* __restrict__ xlo,
+                              const float* __restrict__ w,
+                              const float* __restrict__ lse,
+                              float* __restrict__ partials, int d, int k,
+                              int64_t n, int nchunk) {
+  extern __shared__ float lds[];
+  constexpr int CB = 16 * NCT;          // clusters per block
+  constexpr int WPLANE = CB * MP_WROW;  // bf16 elements per w plane
+  constexpr int BUFB = MP_BUF_BYTES(NCT);
+  char* lds_b = (char*)lds;
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int r16 = lane & 15;
+  const int g4 = lane >> 4;
+  const int chunk = blockIdx.y;
+  const int c0 = blockIdx.x * CB;
+  const int dp = d + 1;
+  const int pp = dp * (dp + 1) / 2;
+  // live 16-row cluster tiles of this block (block-uniform)
+  const int nct = (min(CB, k - c0) + 15) / 16;
+
+  // this lane's pair column per owned tile: z rows (i, j), fixed for the
+  // whole kernel. Columns >= PP (a whole dead tile included) compute on
+  // row 0 and are never stored: no per-tile branch in the k-loop.
+  int zoff_i[TPW], zoff_j[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int p = (wave + 8 * t) * 16 + r16;
+    int i = 0, j = 0;
+    if (p < pp) tri_row_col(p, &i, &j);
+    zoff_i[t] = i * MP_ZROW + 8 * g4;
+    zoff_j[t] = j * MP_ZROW + 8 * g4;
+  }
+
+  f32x4 accA[TPW][NCT], accB[TPW][NCT];  // hi*hi | hi*lo + lo*hi
+#pragma unroll
+  for (int t = 0; t < TPW; ++t)
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+      accA[t][ct] = (f32x4)(0.0f);
+      accB[t][ct] = (f32x4)(0.0f);
+    }
+
+  const int64_t tiles = (n + MP_BK - 1) / MP_BK;
+  // (the 64-bit divide runs on the VALU: readfirstlane keeps the tile
+  // count, and every branch on it, scalar)
+  const int my_tiles = __builtin_amdgcn_readfirstlane(
+      chunk < tiles ? (int)((tiles - chunk + nchunk - 1) / nchunk) : 0);
+  // the one partial tile is the globally last; it is this chunk's last
+  const bool has_tail =
+      (n % MP_BK) != 0 && my_tiles > 0 &&
+      chunk + (int64_t)(my_tiles - 1) * nchunk == tiles - 1;
+
+  // ---- staging: quads of 4 consecutive events --------------------------
+  // x: d*32 quads over 2 x 512 slots, slots past the end repeat the last
+  // quad (same value to the same address) so the path has no branch;
+  // w: CB rows x 32 quads, each thread one event quad of rows cr, cr+16,
+  // ... (lse shared); rows >= K load row K-1 and stage as zero.
+  const int xq_last = d * (MP_BK / 4) - 1;
+  const int eq = threadIdx.x % (MP_BK / 4);
+  const int cr = threadIdx.x / (MP_BK / 4);
+  int xdi[2], xeq[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int q = min((int)threadIdx.x + s * MP_NT, xq_last);
+    xdi[s] = q / (MP_BK / 4);
+    xeq[s] = q % (MP_BK / 4);
+  }
+  uint2 rxh[2], rxl[2];
+  float4 rw[NCT], rl;
+  rl = (float4){0, 0, 0, 0};
+  // full tile: raw vector loads only, so nothing here waits on memory;
+  // __expf(w - lse) and the hi/lo split happen in write_buf, after the
+  // MFMA work of the current tile
+  auto issue_full = [&](int64_t tile) {
+    const int64_t e0 = tile * MP_BK;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int64_t g = (int64_t)xdi[s] * n + e0 + xeq[s] * 4;
+      rxh[s] = *(const uint2*)&xhi[g];
+      rxl[s] = *(const uint2*)&xlo[g];
+    }
+    const int64_t ge = e0 + eq * 4;
+    if (lse) rl = *(const float4*)&lse[ge];
+#pragma unroll
+    for (int s = 0; s < NCT; ++s) {
+      const int cw = min(c0 + cr + 16 * s, k - 1);
+      rw[s] = *(const float4*)&w[(int64_t)cw * n + ge];
+    }
+  };
+  // tail tile: element-wise guarded; pad events carry x = 0 and the w that
+  // stages as 0 (-inf under lse, else 0)
+  auto issue_tail = [&](int64_t tile) {
+    const int64_t e0 = tile * MP_BK;
+    const float wpad = lse ? -INFINITY : 0.0f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int64_t ge = e0 + xeq[s] * 4;
+      const int64_t g = (int64_t)xdi[s] * n + ge;
+      __hip_bfloat16 h[4], l[4];
+      for (int u = 0; u < 4; ++u) {
+        const bool ok = ge + u < n;
+        h[u] = ok ? xhi[g + u] : __hip_bfloat16(0.0f);
+        l[u] = ok ? xlo[g + u] : __hip_bfloat16(0.0f);
+      }
+      rxh[s] = *(uint2*)h;
+      rxl[s] = *(uint2*)l;
+    }
+    const int64_t ge = e0 + eq * 4;
+    float lv[4] = {0, 0, 0, 0};
+    if (lse)
+      for (int u = 0; u < 4; ++u)
+        if (ge + u < n) lv[u] = lse[ge + u];
+    rl = *(float4*)lv;
+#pragma unroll
+    for (int s = 0; s < NCT; ++s) {
+      const int cw = min(c0 + cr + 16 * s, k - 1);
+      const int64_t g = (int64_t)cw * n + ge;
+      float v[4];
+      for (int u = 0; u < 4; ++u) v[u] = ge + u < n ? w[g + u] : wpad;
+      rw[s] = *(float4*)v;
+    }
+  };
+  auto write_buf = [&](int buf) {
+    float* zf = (float*)(lds_b + buf * BUFB);
+    __bf16* wh = (__bf16*)(zf + 32 * MP_ZROW);
+    __bf16* wl = wh + WPLANE;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const __bf16* h = (const __bf16*)&rxh[s];
+      const __bf16* l = (const __bf16*)&rxl[s];
+      float4 z;
+      z.x = (float)h[0] + (float)l[0];
+      z.y = (float)h[1] + (float)l[1];
+      z.z = (float)h[2] + (float)l[2];
+      z.w = (float)h[3] + (float)l[3];
+      *(float4*)(zf + xdi[s] * MP_ZROW + xeq[s] * 4) = z;
+    }
+    // w split into bf16 hi/lo ONCE here, not per consuming wave
+#pragma unroll
+    for (int s = 0; s < NCT; ++s) {
+      float v[4] = {rw[s].x, rw[s].y, rw[s].z, rw[s].w};
+      if (lse) {
+        v[0] = __expf(v[0] - rl.x);
+        v[1] = __expf(v[1] - rl.y);
+        v[2] = __expf(v[2] - rl.z);
+        v[3] = __expf(v[3] - rl.w);
+      }
+      const bool row_ok = c0 + cr + 16 * s < k;
+      __bf16 h[4], l[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float vu = row_ok ? v[u] : 0.0f;
+        h[u] = (__bf16)vu;
+        l[u] = (__bf16)(vu - (float)h[u]);
+      }
+      const int off = (cr + 16 * s) * MP_WROW + eq * 4;
+      *(uint2*)(wh + off) = *(const uint2*)h;
+      *(uint2*)(wl + off) = *(const uint2*)l;
+    }
+  };
+  // one staged tile: 4 k-steps of 32 events. ALLCT drops the per-cluster-
+  // tile branch from the full-block path.
+  auto compute = [&](auto allct, int buf) {
+    constexpr bool ALLCT = decltype(allct)::value;
+    const float* zf = (const float*)(lds_b + buf * BUFB);
+    const __bf16* wh = (const __bf16*)(zf + 32 * MP_ZROW);
+    const __bf16* wl = wh + WPLANE;
+#pragma unroll 1
+    for (int ks = 0; ks < MP_BK / 32; ++ks) {
+      bf16x8 a_hi[NCT], a_lo[NCT];
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) {
+        const int aoff = (ct * 16 + r16) * MP_WROW + ks * 32 + 8 * g4;
+        a_hi[ct] = *(const bf16x8*)(wh + aoff);
+        a_lo[ct] = *(const bf16x8*)(wl + aoff);
+      }
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) {
+        // B fragment: 8 events of pair column (i, j), built in registers
+        const float* zi = zf + zoff_i[t] + ks * 32;
+        const float* zj = zf + zoff_j[t] + ks * 32;
+        const float4 i0 = *(const float4*)zi;
+        const float4 i1 = *(const float4*)(zi + 4);
+        const float4 j0 = *(const float4*)zj;
+        const float4 j1 = *(const float4*)(zj + 4);
+        const float pr[8] = {i0.x * j0.x, i0.y * j0.y, i0.z * j0.z,
+                             i0.w * j0.w, i1.x * j1.x, i1.y * j1.y,
+                             i1.z * j1.z, i1.w * j1.w};
+        bf16x8 b_hi, b_lo;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const __bf16 hi = (__bf16)pr[u];
+          b_hi[u] = hi;
+          b_lo[u] = (__bf16)(pr[u] - (float)hi);
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+          if (ALLCT || ct < nct) {
+            accA[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a_hi[ct], b_hi, accA[t][ct], 0, 0, 0);
+            accB[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a_hi[ct], b_lo, accB[t][ct], 0, 0, 0);
+            accB[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a_lo[ct], b_hi, accB[t][ct], 0, 0, 0);
+          }
+        }
+      }
+    }
+  };
+  // double-buffered, register-staged tiles (T14): tile t+1's loads are
+  // issued before tile t's MFMA work and written to the other buffer after
+  // it. One barrier per tile: the write targets the buffer nobody reads
+  // this iteration, and the previous barrier already ordered its readers.
+  // The tail tile runs after the loop, un-pipelined, so the loop holds
+  // only the full-tile loads (ledger R3: a shared full/tail path makes the
+  // compiler wait on the loads where they are issued).
+  const int nfull = my_tiles - (has_tail ? 1 : 0);
+  auto main_loop = [&](auto allct) {
+    int cur = 0;
+    for (int ti = 0; ti < nfull; ++ti) {
+      const bool more = ti + 1 < nfull;
+      if (more) issue_full(chunk + (int64_t)(ti + 1) * nchunk);
+      compute(allct, cur);
+      if (more) write_buf(cur ^ 1);
+      __syncthreads();
+      cur ^= 1;
+    }
+    if (has_tail) {  // every reader of both buffers is past a barrier
+      issue_tail(tiles - 1);
+      write_buf(cur);
+      __syncthreads();
+      compute(allct, cur);
+    }
+  };
+
+  // constant z rows (ones at d, zeros above) in BOTH buffers, written once
+  for (int b = 0; b < 2; ++b) {
+    float* zf = (float*)(lds_b + b * BUFB);
+    for (int idx = d * MP_BK + threadIdx.x; idx < 32 * MP_BK;
+         idx += MP_NT) {
+      const int di = idx / MP_BK, ei = idx % MP_BK;
+      zf[di * MP_ZROW + ei] = di == d ? 1.0f : 0.0f;
+    }
+  }
+  if (nfull > 0) {
+    issue_full(chunk);
+    write_buf(0);
+  }
+  __syncthreads();
+  if (nct == NCT)
+    main_loop(std::true_type{});
+  else
+    main_loop(std::false_type{});
+
+  // C/D layout (16x16): col = l&15 (pair), row = 4*(l>>4) + reg (cluster)
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int p = (wave + 8 * t) * 16 + r16;
+    if (p < pp) {
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = c0 + ct * 16 + 4 * g4 + r;
+          if (c < k)
+            partials[((int64_t)chunk * k + c) * pp + p] =
+                accA[t][ct][r] + accB[t][ct][r];
+        }
+      }
+    }
+  }
+}
+
+// w[c, e] = __expf(logw[c, e] - lse[e]) materialised with the same intrinsic
+// the moments kernels apply at staging (lets a test feed either form).
+__global__ void __launch_bounds__(NT)
+exp_sub_lse_kernel(const float* __restrict__ logw,
+                   const float* __restrict__ lse, float* __restrict__ out,
+                   int k, int64_t n) {
+  const int64_t total = (int64_t)k * n;
+  for (int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * NT)
+    out[idx] = __expf(logw[idx] - lse[idx % n]);
 }
 
 // ---------------------------------------------------------------------------
