@@ -273,7 +273,12 @@ def estep_fused_lds(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
     n = z.shape[1]
     nblk = (n + 127) // 128
     partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
-    hip_ext().estep_fused_lds(z, mfac, add, w_out, partial)
+    # GMM_ESTEP_LDS=legacy selects the first version of the kernel
+    # (same-build A/B); the log-weights of the two are bitwise equal
+    if os.environ.get("GMM_ESTEP_LDS", "lds2") == "legacy":
+        hip_ext().estep_fused_lds(z, mfac, add, w_out, partial)
+    else:
+        hip_ext().estep_fused_lds2(z, mfac, add, w_out, partial)
     if not need_lik:
         return w_out, None
     lik = torch.empty(1, dtype=torch.float32, device=z.device)

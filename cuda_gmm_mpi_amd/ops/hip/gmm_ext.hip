@@ -445,6 +445,42 @@ void estep_fused_lds(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
   HIP_CHECK(hipGetLastError());
 }
 
+// Same contract and LDS budget as estep_fused_lds; the default small-K path.
+void estep_fused_lds2(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
+                      torch::Tensor w_out, torch::Tensor partial) {
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
+                  z.scalar_type() == torch::kBFloat16,
+              "z must be contiguous bf16 [D,N]");
+  TORCH_CHECK(mfac.is_contiguous() && mfac.scalar_type() == torch::kBFloat16,
+              "mfac must be bf16");
+  check_f32(add, "add");
+  check_f32(w_out, "w_out");
+  check_f32(partial, "partial");
+  const int d = (int)z.size(0);
+  const int64_t n = z.size(1);
+  const int k = (int)add.size(0);
+  TORCH_CHECK(d >= 1 && d <= 31, "estep_fused_lds2 needs 1 <= D <= 31");
+  TORCH_CHECK(k >= 1 && n >= 1, "estep_fused_lds2 needs K >= 1 and N >= 1");
+  TORCH_CHECK(mfac.numel() >= (int64_t)k * 2 * 32 * 32, "mfac too small");
+  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
+  const int64_t nblk = (n + 128 - 1) / 128;
+  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
+  const size_t zbytes = (size_t)128 * 40 * 2;  // transposed z tile
+  const size_t lds = zbytes + sizeof(float) * (size_t)k * (128 + 4);
+  TORCH_CHECK(lds <= 64 * 1024,
+              "estep_fused_lds2 LDS budget exceeded (K too big)");
+  // 16-byte posterior stores need every row start 16-byte aligned
+  const int vec4 =
+      n % 4 == 0 && reinterpret_cast<uintptr_t>(w_out.data_ptr()) % 16 == 0;
+  hipLaunchKernelGGL(gmm::estep_fused_lds2_kernel, dim3((uint32_t)nblk),
+                     dim3(kNT), lds, stream(),
+                     reinterpret_cast<const __hip_bfloat16*>(z.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(mfac.data_ptr()),
+                     add.data_ptr<float>(), w_out.data_ptr<float>(),
+                     partial.data_ptr<float>(), d, k, n, vec4);
+  HIP_CHECK(hipGetLastError());
+}
+
 void estep_fused_f32_lds(torch::Tensor z, torch::Tensor mfac32,
                          torch::Tensor add, torch::Tensor w_out,
                          torch::Tensor partial) {
@@ -829,6 +865,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "exact-f32 MFMA fused E-step (D <= 31)");
   m.def("estep_fused_lds", &estep_fused_lds,
         "small-K fused E-step (v1, lw in LDS, posteriors written)");
+  m.def("estep_fused_lds2", &estep_fused_lds2,
+        "small-K fused E-step (register B tiles, float4 pass 2; default)");
   m.def("estep_fused_f32_lds", &estep_fused_f32_lds,
         "small-K exact-f32 fused E-step (v1)");
   m.def("estep_fused", &estep_fused,

@@ -2015,6 +2015,273 @@ estep_fused_lds_kernel(const __hip_bfloat16* __restrict__ z,
 }
 
 // ---------------------------------------------------------------------------
+// Small-K fused E-step, second version (the default; the kernel above stays
+// reachable as GMM_ESTEP_LDS=legacy). Same contract, same LDS footprint and
+// bitwise the same log-weights; three things differ (134 VGPRs, no AGPRs,
+// no scratch: 3 waves per SIMD, the limit the LDS sets anyway):
+//  - staging: a work item is (event, k-octet). It issues its <= 8 coalesced
+//    2-byte loads back to back, waits once, and writes one 16-byte LDS store
+//    with the ones-row and the zero pad already in place;
+//  - MFMA phase: the 8 B fragments of the block's 4 event tiles are read once
+//    and held in registers; per cluster 4 independent accumulators (arch
+//    VGPRs: the launch bound keeps the register budget under 256, so the
+//    compiler does not pick the AGPR form) run with no LDS read in the loop,
+//    and a permlane32_swap of two tiles' half sums lets all 64 lanes finish
+//    and store a log-weight;
+//  - pass 2: a thread owns 4 consecutive events of one cluster slice
+//    (clusters s, s+8, ...), reads and rewrites lw as float4 and stores the
+//    posteriors as float4 when n % 4 == 0. The 8 slices combine max and sum
+//    through the z tile's LDS, which is dead by then.
+// ---------------------------------------------------------------------------
+#define ESTL2_NS 8  // cluster slices in pass 2 (NT / 32)
+
+__global__ void __launch_bounds__(NT, 3)
+estep_fused_lds2_kernel(const __hip_bfloat16* __restrict__ z,
+                        const __hip_bfloat16* __restrict__ mfac,  // [K][2][32][32]
+                        const float* __restrict__ add,            // const + ln pi
+                        float* __restrict__ w_out,
+                        float* __restrict__ partial, int d, int k, int64_t n,
+                        int vec4) {
+  // LDS: zs_t [ESTL_BE][ESTL_ZROW] bf16 as in the kernel above (reused in
+  // pass 2 as cmax/csum [ESTL2_NS][ESTL_BE] f32), then lw [k][ESTL_BE+4] f32.
+  extern __shared__ float lds[];
+  constexpr int lrow = ESTL_BE + 4;
+  __hip_bfloat16* zs = (__hip_bfloat16*)lds;
+  float* lw = lds + (ESTL_BE * ESTL_ZROW) / 2;
+
+  // wave-uniform by construction; readfirstlane lets the compiler keep the
+  // row and cluster indices (and their 64-bit address products) in SGPRs
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t e0 = (int64_t)blockIdx.x * ESTL_BE;
+  const int cnt = (int)min((int64_t)ESTL_BE, n - e0);
+
+  // staging: items (event e, octet o), 128 x 4 = 2 per thread; lanes run
+  // along e. Octet slot i holds row 8o+i: data below d, the constant 1 at
+  // d, zero above. Rows >= d load row d-1 (a valid address) and drop it, so
+  // every load is issued before the first wait.
+  {
+    const unsigned short* zu = (const unsigned short*)z;
+    const int e = threadIdx.x & (ESTL_BE - 1);
+    const int o_lo = wave >> 1;  // items o_lo and o_lo + 2 (tid >> 7)
+    unsigned short v[2][8];
+    if (cnt == ESTL_BE) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int row = min(8 * (o_lo + 2 * it) + i, d - 1);
+          v[it][i] = zu[(int64_t)row * n + e0 + e];
+        }
+    } else {
+      const int ec = min(e, cnt - 1);
+#pragma unroll
+      for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int row = min(8 * (o_lo + 2 * it) + i, d - 1);
+          const unsigned short x = zu[(int64_t)row * n + e0 + ec];
+          v[it][i] = (e < cnt) ? x : (unsigned short)0;
+        }
+    }
+    const unsigned short one = (e < cnt) ? 0x3F80 : 0;  // bf16 1.0
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int o = o_lo + 2 * it;
+      unsigned int p[4];
+#pragma unroll
+      for (int i = 0; i < 8; i += 2) {
+        const int r0 = 8 * o + i, r1 = r0 + 1;
+        const unsigned int lo = r0 < d ? v[it][i] : (r0 == d ? one : 0);
+        const unsigned int hi = r1 < d ? v[it][i + 1] : (r1 == d ? one : 0);
+        p[i >> 1] = lo | (hi << 16);
+      }
+      *(uint4*)(zs + e * ESTL_ZROW + 8 * o) = make_uint4(p[0], p[1], p[2], p[3]);
+    }
+  }
+  __syncthreads();
+
+  // MFMA phase: fragment maps as in the kernel above; waves split the
+  // cluster loop (c = wave, wave+4, ...).
+  const int j32 = lane & 31;
+  const int g2 = lane >> 5;
+  typedef __attribute__((ext_vector_type(16))) float f32x16;
+  const bf16x8* mf = (const bf16x8*)mfac;  // rows of 32 bf16 = 4 frags each
+  const int fq0 = g2;      // chunk 0 covers k [0,16): slots {0,1}
+  const int fq1 = 2 + g2;  // chunk 1 covers k [16,32): slots {2,3}
+  const int nwaves = NT / WAVE;
+
+  // the B fragments do not depend on the cluster: read them once
+  bf16x8 b0[ESTL_BE / 32], b1[ESTL_BE / 32];
+#pragma unroll
+  for (int t = 0; t < ESTL_BE / 32; ++t) {
+    b0[t] = *(const bf16x8*)(zs + (t * 32 + j32) * ESTL_ZROW + 8 * g2);
+    b1[t] = *(const bf16x8*)(zs + (t * 32 + j32) * ESTL_ZROW + 16 + 8 * g2);
+  }
+  struct Fac {
+    bf16x8 h0, l0, h1, l1;
+    float add;
+  };
+  auto load_fac = [&](Fac& f, int c) {
+    const int64_t base = ((int64_t)c * 2) * 32 * 4;  // in bf16x8 units
+    f.h0 = mf[base + j32 * 4 + fq0];
+    f.l0 = mf[base + 32 * 4 + j32 * 4 + fq0];
+    f.h1 = mf[base + j32 * 4 + fq1];
+    f.l1 = mf[base + 32 * 4 + j32 * 4 + fq1];
+    f.add = add[c];
+  };
+  auto cluster = [&](const Fac& f, int c) {
+    // 4 independent chains, each in the order of the kernel above
+    // (hi.b0, hi.b1, lo.b0, lo.b1), issued tile-interleaved
+    f32x16 y[ESTL_BE / 32];
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; ++t)
+      y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          f.h0, b0[t], (f32x16)(0.0f), 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; ++t)
+      y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h1, b1[t], y[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; ++t)
+      y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l0, b0[t], y[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; ++t)
+      y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l1, b1[t], y[t], 0, 0, 0);
+    float s[ESTL_BE / 32];
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; ++t) {
+      s[t] = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[t] = fmaf(y[t][r], y[t][r], s[t]);
+    }
+    // the 32 Y rows live across the two lane halves. Swap the upper half of
+    // tile t with the lower half of tile t+1: lanes 0-31 then hold both
+    // halves of tile t, lanes 32-63 both of tile t+1 (lower half first in
+    // either, as in the __shfl_xor sum above), and every lane stores
+#pragma unroll
+    for (int t = 0; t < ESTL_BE / 32; t += 2) {
+      const auto sw = __builtin_amdgcn_permlane32_swap(
+          __float_as_uint(s[t]), __float_as_uint(s[t + 1]), false, false);
+      const float st = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+      lw[c * lrow + (t + g2) * 32 + j32] = -0.5f * st + f.add;
+    }
+  };
+  // one-deep factor prefetch over two register sets: the next cluster's
+  // loads are issued before this cluster's MFMAs and first waited for a
+  // whole cluster later (one set and a copy put the wait mid-cluster).
+  // The prefetch is unconditional (past the end it re-loads cluster k-1):
+  // a load under a branch makes the number of loads in flight depend on
+  // the path, and the compiler then waits for all of them.
+  Fac fa, fb;
+  int c = wave;
+  load_fac(fa, min(c, k - 1));
+  for (; c + nwaves < k; c += 2 * nwaves) {  // two clusters, one basic block
+    // the scheduling barriers keep each prefetch ahead of the cluster it
+    // overlaps and the two clusters' accumulators from being live together
+    load_fac(fb, c + nwaves);
+    __builtin_amdgcn_sched_barrier(0);
+    cluster(fa, c);
+    __builtin_amdgcn_sched_barrier(0);
+    load_fac(fa, min(c + 2 * nwaves, k - 1));
+    __builtin_amdgcn_sched_barrier(0);
+    cluster(fb, c + nwaves);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (c < k) cluster(fa, c);  // odd count: fa already holds cluster c
+  __syncthreads();
+
+  // pass 2: thread = (event group g: events 4g..4g+3, cluster slice sl).
+  // An empty slice (sl >= k) contributes -3e38 to the max and 0 to the sum.
+  float4* lw4 = (float4*)lw;                  // row stride lrow / 4 = 33
+  float4* cmax = (float4*)lds;                // [ESTL2_NS][32]
+  float4* csum = cmax + ESTL2_NS * 32;        // [ESTL2_NS][32]
+  const int g = threadIdx.x & 31;
+  const int sl = threadIdx.x >> 5;
+  float4 m = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
+#pragma unroll 4
+  for (int c = sl; c < k; c += ESTL2_NS) {
+    const float4 x = lw4[c * (lrow / 4) + g];
+    m.x = fmaxf(m.x, x.x);
+    m.y = fmaxf(m.y, x.y);
+    m.z = fmaxf(m.z, x.z);
+    m.w = fmaxf(m.w, x.w);
+  }
+  cmax[sl * 32 + g] = m;
+  __syncthreads();
+  m = cmax[g];
+#pragma unroll
+  for (int q = 1; q < ESTL2_NS; ++q) {
+    const float4 x = cmax[q * 32 + g];
+    m.x = fmaxf(m.x, x.x);
+    m.y = fmaxf(m.y, x.y);
+    m.z = fmaxf(m.z, x.z);
+    m.w = fmaxf(m.w, x.w);
+  }
+  float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 4
+  for (int c = sl; c < k; c += ESTL2_NS) {
+    float4 x = lw4[c * (lrow / 4) + g];
+    x.x = __expf(x.x - m.x);
+    x.y = __expf(x.y - m.y);
+    x.z = __expf(x.z - m.z);
+    x.w = __expf(x.w - m.w);
+    lw4[c * (lrow / 4) + g] = x;
+    sum.x += x.x;
+    sum.y += x.y;
+    sum.z += x.z;
+    sum.w += x.w;
+  }
+  csum[sl * 32 + g] = sum;
+  __syncthreads();
+  float4 total = csum[g];
+#pragma unroll
+  for (int q = 1; q < ESTL2_NS; ++q) {
+    const float4 x = csum[q * 32 + g];
+    total.x += x.x;
+    total.y += x.y;
+    total.z += x.z;
+    total.w += x.w;
+  }
+  const float4 inv = make_float4(1.0f / total.x, 1.0f / total.y,
+                                 1.0f / total.z, 1.0f / total.w);
+  const int left = cnt - 4 * g;  // valid events of this group (may be <= 0)
+  if (vec4) {
+    // n % 4 == 0: cnt is a multiple of 4, a group is all valid or all pad
+    if (left > 0) {
+#pragma unroll 4
+      for (int c = sl; c < k; c += ESTL2_NS) {
+        const float4 x = lw4[c * (lrow / 4) + g];
+        *(float4*)(w_out + (int64_t)c * n + e0 + 4 * g) =
+            make_float4(x.x * inv.x, x.y * inv.y, x.z * inv.z, x.w * inv.w);
+      }
+    }
+  } else {
+#pragma unroll 2
+    for (int c = sl; c < k; c += ESTL2_NS) {
+      const float4 x = lw4[c * (lrow / 4) + g];
+      float* dst = w_out + (int64_t)c * n + e0 + 4 * g;
+      if (left > 0) dst[0] = x.x * inv.x;
+      if (left > 1) dst[1] = x.y * inv.y;
+      if (left > 2) dst[2] = x.z * inv.z;
+      if (left > 3) dst[3] = x.w * inv.w;
+    }
+  }
+  // likelihood: slice 0 is lanes 0-31 of wave 0 and holds all 128 events
+  if (wave == 0) {
+    float acc = 0.0f;
+    if (sl == 0) {
+      if (left > 0) acc += m.x + __logf(total.x);
+      if (left > 1) acc += m.y + __logf(total.y);
+      if (left > 2) acc += m.z + __logf(total.z);
+      if (left > 3) acc += m.w + __logf(total.w);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+      acc += __shfl_down(acc, off, WAVE);
+    if (lane == 0) partial[blockIdx.x] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Exact-fp32 fused E-step (D <= 31): same structure as estep_fused_lds_kernel
 // but on v_mfma_f32_32x32x2_f32 — f32 in / f32 accumulate, bitwise an fmaf
 // chain (guide §3), consuming the fp32 factor plane. 16 dependent MFMAs
@@ -2043,10 +2310,18 @@ estep_fused_f32_lds_kernel(const float* __restrict__ z,
   const int cnt = (int)min((int64_t)ESTL_BE, n - e0);
 
   if (cnt == ESTL_BE) {
-    for (int idx = threadIdx.x; idx < d * ESTL_BE; idx += blockDim.x) {
-      const int kk = idx / ESTL_BE, ei = idx % ESTL_BE;
-      zs[ei * ZR + kk] = z[(int64_t)kk * n + e0 + ei];
-    }
+    // all of a thread's loads are issued before the first is used (one
+    // wait per block, not one per row pair); rows >= d load row d-1 and
+    // are not stored
+    constexpr int NIT = 32 * ESTL_BE / NT;  // 16 row pairs cover d <= 31
+    const int ei = threadIdx.x % ESTL_BE, k0 = threadIdx.x / ESTL_BE;
+    float v[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      v[it] = z[(int64_t)min(k0 + 2 * it, d - 1) * n + e0 + ei];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      if (k0 + 2 * it < d) zs[ei * ZR + k0 + 2 * it] = v[it];
   } else {
     for (int idx = threadIdx.x; idx < d * ESTL_BE; idx += blockDim.x) {
       const int kk = idx / ESTL_BE, ei = idx % ESTL_BE;
