@@ -227,6 +227,23 @@ def constants(r: torch.Tensor, means: torch.Tensor | None = None,
     return rinv_c, const_c
 
 
+def _run_fused(entry: str, tile: int, z: torch.Tensor, fac: torch.Tensor,
+               add: torch.Tensor, w_out: torch.Tensor, need_lik: bool,
+               *lse: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """Launch one fused E-step entry point (`tile` events per block) and
+    reduce its per-block likelihood partials."""
+    ext = hip_ext()
+    nblk = (z.shape[1] + tile - 1) // tile
+    # every launched block writes its partial slot: no zero-fill needed
+    partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
+    getattr(ext, entry)(z, fac, add, w_out, *lse, partial)
+    if not need_lik:
+        return w_out, None
+    lik = torch.empty(1, dtype=torch.float32, device=z.device)
+    ext.reduce_scalar(partial, lik)
+    return w_out, lik
+
+
 def estep_fused(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
                 w_out: torch.Tensor, lse: torch.Tensor,
                 need_lik: bool = True
@@ -235,16 +252,7 @@ def estep_fused(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
     per-event log-sum-exp into lse [N], returns (w_out, likelihood).
     Online-softmax over 256-event blocks; the lse-aware M-step applies
     exp(w_out - lse) on the fly — posteriors are never materialized."""
-    n = z.shape[1]
-    nblk = (n + 255) // 256
-    # every launched block writes its partial slot: no zero-fill needed
-    partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
-    hip_ext().estep_fused(z, mfac, add, w_out, lse, partial)
-    if not need_lik:
-        return w_out, None
-    lik = torch.empty(1, dtype=torch.float32, device=z.device)
-    hip_ext().reduce_scalar(partial, lik)
-    return w_out, lik
+    return _run_fused("estep_fused", 256, z, mfac, add, w_out, need_lik, lse)
 
 
 def estep_fused_available(device: torch.device, dtype: str, d: int,
@@ -270,20 +278,11 @@ def estep_fused_lds(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
                     w_out: torch.Tensor, need_lik: bool = True
                     ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """v1 fused bf16 E-step: POSTERIORS into w_out, likelihood scalar."""
-    n = z.shape[1]
-    nblk = (n + 127) // 128
-    partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
     # GMM_ESTEP_LDS=legacy selects the first version of the kernel
     # (same-build A/B); the log-weights of the two are bitwise equal
-    if os.environ.get("GMM_ESTEP_LDS", "lds2") == "legacy":
-        hip_ext().estep_fused_lds(z, mfac, add, w_out, partial)
-    else:
-        hip_ext().estep_fused_lds2(z, mfac, add, w_out, partial)
-    if not need_lik:
-        return w_out, None
-    lik = torch.empty(1, dtype=torch.float32, device=z.device)
-    hip_ext().reduce_scalar(partial, lik)
-    return w_out, lik
+    legacy = os.environ.get("GMM_ESTEP_LDS", "lds2") == "legacy"
+    return _run_fused("estep_fused_lds" if legacy else "estep_fused_lds2",
+                      128, z, mfac, add, w_out, need_lik)
 
 
 def estep_fused_f32_lds(z: torch.Tensor, mfac32: torch.Tensor,
@@ -291,15 +290,8 @@ def estep_fused_f32_lds(z: torch.Tensor, mfac32: torch.Tensor,
                         need_lik: bool = True
                         ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """v1 exact-f32 fused E-step: POSTERIORS into w_out."""
-    n = z.shape[1]
-    nblk = (n + 127) // 128
-    partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
-    hip_ext().estep_fused_f32_lds(z, mfac32, add, w_out, partial)
-    if not need_lik:
-        return w_out, None
-    lik = torch.empty(1, dtype=torch.float32, device=z.device)
-    hip_ext().reduce_scalar(partial, lik)
-    return w_out, lik
+    return _run_fused("estep_fused_f32_lds", 128, z, mfac32, add, w_out,
+                      need_lik)
 
 
 def estep_fused_f32(z: torch.Tensor, mfac32: torch.Tensor, add: torch.Tensor,
@@ -308,15 +300,8 @@ def estep_fused_f32(z: torch.Tensor, mfac32: torch.Tensor, add: torch.Tensor,
                     ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """Exact-f32 MFMA fused E-step (CUDA, D <= 31, any K): log weights
     into w_out, per-event log-sum-exp into lse."""
-    n = z.shape[1]
-    nblk = (n + 255) // 256
-    partial = torch.empty(nblk, dtype=torch.float32, device=z.device)
-    hip_ext().estep_fused_f32(z, mfac32, add, w_out, lse, partial)
-    if not need_lik:
-        return w_out, None
-    lik = torch.empty(1, dtype=torch.float32, device=z.device)
-    hip_ext().reduce_scalar(partial, lik)
-    return w_out, lik
+    return _run_fused("estep_fused_f32", 256, z, mfac32, add, w_out,
+                      need_lik, lse)
 
 
 def estep_big_available(device: torch.device, dtype: str, d: int) -> bool:

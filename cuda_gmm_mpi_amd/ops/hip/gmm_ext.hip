@@ -210,8 +210,8 @@ void constants(torch::Tensor r, torch::Tensor means, torch::Tensor pi,
     mp32 = mfac32.data_ptr<float>();
   }
   if (make_mfac) {
-    const int rows = ((d + 31) / 32) * 32;
-    const int kct = d + 1 <= 32 ? 2 : d + 1 <= 48 ? 3 : d + 1 <= 80 ? 5 : 9;
+    const int rows = gmm::mfac_rows(d);
+    const int kct = gmm::mfac_kct(d);
     TORCH_CHECK(mfac.is_cuda() && mfac.is_contiguous() &&
                     mfac.scalar_type() == torch::kBFloat16 &&
                     mfac.numel() == (int64_t)k * 2 * rows * kct * 16 &&
@@ -380,131 +380,132 @@ void exp_sub_lse(torch::Tensor logw, torch::Tensor lse, torch::Tensor out) {
   HIP_CHECK(hipGetLastError());
 }
 
-void estep_fused(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
-                 torch::Tensor w_out, torch::Tensor lse_out,
-                 torch::Tensor partial) {
-  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
-                  z.scalar_type() == torch::kBFloat16,
-              "z must be contiguous bf16 [D,N]");
-  TORCH_CHECK(mfac.is_contiguous() && mfac.scalar_type() == torch::kBFloat16,
-              "mfac must be bf16");
+// The five fused small-D E-step entry points: z [D,N] and the factor table
+// in the precision of Fac, add [K], w_out [K,N], one partial per block of
+// `tile` events.
+struct FusedShape {
+  int d, k;
+  int64_t n, nblk;
+};
+
+template <typename Fac>
+FusedShape check_fused(const char* name, const torch::Tensor& z,
+                       const torch::Tensor& fac, const torch::Tensor& add,
+                       const torch::Tensor& w_out,
+                       const torch::Tensor& partial, int tile) {
+  constexpr bool f32 = std::is_same<typename Fac::In, float>::value;
+  const auto dt = f32 ? torch::kFloat32 : torch::kBFloat16;
+  const char* dtn = f32 ? "fp32" : "bf16";
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == dt &&
+                  z.dim() == 2,
+              name, ": z must be contiguous ", dtn, " [D,N] on device");
+  TORCH_CHECK(fac.is_cuda() && fac.is_contiguous() && fac.scalar_type() == dt,
+              name, ": factor table must be contiguous ", dtn, " on device");
   check_f32(add, "add");
   check_f32(w_out, "w_out");
   check_f32(partial, "partial");
-  const int d = (int)z.size(0);
-  const int64_t n = z.size(1);
-  const int k = (int)add.size(0);
-  TORCH_CHECK(d <= 31, "estep_fused needs D <= 31");
-  TORCH_CHECK(mfac.numel() >= (int64_t)k * 2 * 32 * 32, "mfac too small");
-  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
-  const int64_t nblk = (n + 256 - 1) / 256;
-  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
-  // transposed z tile + per-wave online-softmax state + lse (K-independent)
-  const size_t lds = (size_t)256 * 40 * 2 +
-                     sizeof(float) * (2 * (256 / 64) * 256 + 256);
+  FusedShape s;
+  s.d = (int)z.size(0);
+  s.n = z.size(1);
+  s.k = (int)add.size(0);
+  s.nblk = (s.n + tile - 1) / tile;
+  TORCH_CHECK(s.d >= 1 && s.d <= 31, name, " needs 1 <= D <= 31");
+  TORCH_CHECK(s.k >= 1 && s.n >= 1, name, " needs K >= 1 and N >= 1");
+  TORCH_CHECK(fac.numel() >= (int64_t)s.k * Fac::CELLS, name,
+              ": factor table too small");
+  TORCH_CHECK(w_out.dim() == 2 && w_out.size(0) == s.k &&
+                  w_out.size(1) == s.n,
+              name, ": w_out must be [K,N]");
+  TORCH_CHECK(partial.size(0) >= s.nblk, name, ": partial buffer too small");
+  return s;
+}
+
+// LDS bytes of the lw-in-LDS kernels at K clusters, checked against 64 KB
+template <typename Fac>
+size_t fused_lds_budget(const char* name, int k) {
+  const size_t lds = gmm::estl_lds_bytes<Fac>(k);
+  TORCH_CHECK(lds <= 64 * 1024, name, " LDS budget exceeded (K too big)");
+  return lds;
+}
+
+template <typename Fac, typename Kernel>
+void launch_fused_lse(const char* name, Kernel kernel, const torch::Tensor& z,
+                      const torch::Tensor& fac, const torch::Tensor& add,
+                      torch::Tensor& w_out, torch::Tensor& lse_out,
+                      torch::Tensor& partial) {
+  using In = typename Fac::In;
+  const FusedShape s =
+      check_fused<Fac>(name, z, fac, add, w_out, partial, gmm::EST_BE);
   check_f32(lse_out, "lse_out");
-  TORCH_CHECK(lse_out.numel() == n, "lse_out must be [N]");
-  hipLaunchKernelGGL(gmm::estep_fused_kernel, dim3((uint32_t)nblk), dim3(kNT),
-                     lds, stream(),
-                     reinterpret_cast<const __hip_bfloat16*>(z.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(mfac.data_ptr()),
+  TORCH_CHECK(lse_out.numel() == s.n, name, ": lse_out must be [N]");
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)s.nblk), dim3(kNT),
+                     gmm::est_lds_bytes<Fac>(), stream(), data_as<In>(z),
+                     data_as<In>(fac), add.data_ptr<float>(),
+                     w_out.data_ptr<float>(), lse_out.data_ptr<float>(),
+                     partial.data_ptr<float>(), s.d, s.k, s.n);
+  HIP_CHECK(hipGetLastError());
+}
+
+void estep_fused(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
+                 torch::Tensor w_out, torch::Tensor lse_out,
+                 torch::Tensor partial) {
+  launch_fused_lse<gmm::FacB16>("estep_fused", gmm::estep_fused_kernel, z,
+                                mfac, add, w_out, lse_out, partial);
+}
+
+void estep_fused_f32(torch::Tensor z, torch::Tensor mfac32,
+                     torch::Tensor add, torch::Tensor w_out,
+                     torch::Tensor lse_out, torch::Tensor partial) {
+  launch_fused_lse<gmm::FacF32>("estep_fused_f32",
+                                gmm::estep_fused_f32_kernel, z, mfac32, add,
+                                w_out, lse_out, partial);
+}
+
+template <typename Fac, typename Kernel>
+void launch_fused_lds(const char* name, Kernel kernel, const torch::Tensor& z,
+                      const torch::Tensor& fac, const torch::Tensor& add,
+                      torch::Tensor& w_out, torch::Tensor& partial) {
+  using In = typename Fac::In;
+  const FusedShape s =
+      check_fused<Fac>(name, z, fac, add, w_out, partial, gmm::ESTL_BE);
+  const size_t lds = fused_lds_budget<Fac>(name, s.k);
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)s.nblk), dim3(kNT), lds,
+                     stream(), data_as<In>(z), data_as<In>(fac),
                      add.data_ptr<float>(), w_out.data_ptr<float>(),
-                     lse_out.data_ptr<float>(),
-                     partial.data_ptr<float>(), d, k, n);
+                     partial.data_ptr<float>(), s.d, s.k, s.n);
   HIP_CHECK(hipGetLastError());
 }
 
 void estep_fused_lds(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
                      torch::Tensor w_out, torch::Tensor partial) {
-  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
-                  z.scalar_type() == torch::kBFloat16,
-              "z must be contiguous bf16 [D,N]");
-  TORCH_CHECK(mfac.is_contiguous() && mfac.scalar_type() == torch::kBFloat16,
-              "mfac must be bf16");
-  check_f32(add, "add");
-  check_f32(w_out, "w_out");
-  check_f32(partial, "partial");
-  const int d = (int)z.size(0);
-  const int64_t n = z.size(1);
-  const int k = (int)add.size(0);
-  TORCH_CHECK(d <= 31, "estep_fused_lds needs D <= 31");
-  TORCH_CHECK(mfac.numel() >= (int64_t)k * 2 * 32 * 32, "mfac too small");
-  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
-  const int64_t nblk = (n + 128 - 1) / 128;
-  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
-  const size_t zbytes = (size_t)128 * 40 * 2;  // transposed z tile
-  const size_t lds = zbytes + sizeof(float) * (size_t)k * (128 + 4);
-  TORCH_CHECK(lds <= 64 * 1024,
-              "estep_fused_lds LDS budget exceeded (K too big)");
-  hipLaunchKernelGGL(gmm::estep_fused_lds_kernel, dim3((uint32_t)nblk),
-                     dim3(kNT), lds, stream(),
-                     reinterpret_cast<const __hip_bfloat16*>(z.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(mfac.data_ptr()),
-                     add.data_ptr<float>(), w_out.data_ptr<float>(),
-                     partial.data_ptr<float>(), d, k, n);
-  HIP_CHECK(hipGetLastError());
-}
-
-// Same contract and LDS budget as estep_fused_lds; the default small-K path.
-void estep_fused_lds2(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
-                      torch::Tensor w_out, torch::Tensor partial) {
-  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
-                  z.scalar_type() == torch::kBFloat16,
-              "z must be contiguous bf16 [D,N]");
-  TORCH_CHECK(mfac.is_contiguous() && mfac.scalar_type() == torch::kBFloat16,
-              "mfac must be bf16");
-  check_f32(add, "add");
-  check_f32(w_out, "w_out");
-  check_f32(partial, "partial");
-  const int d = (int)z.size(0);
-  const int64_t n = z.size(1);
-  const int k = (int)add.size(0);
-  TORCH_CHECK(d >= 1 && d <= 31, "estep_fused_lds2 needs 1 <= D <= 31");
-  TORCH_CHECK(k >= 1 && n >= 1, "estep_fused_lds2 needs K >= 1 and N >= 1");
-  TORCH_CHECK(mfac.numel() >= (int64_t)k * 2 * 32 * 32, "mfac too small");
-  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
-  const int64_t nblk = (n + 128 - 1) / 128;
-  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
-  const size_t zbytes = (size_t)128 * 40 * 2;  // transposed z tile
-  const size_t lds = zbytes + sizeof(float) * (size_t)k * (128 + 4);
-  TORCH_CHECK(lds <= 64 * 1024,
-              "estep_fused_lds2 LDS budget exceeded (K too big)");
-  // 16-byte posterior stores need every row start 16-byte aligned
-  const int vec4 =
-      n % 4 == 0 && reinterpret_cast<uintptr_t>(w_out.data_ptr()) % 16 == 0;
-  hipLaunchKernelGGL(gmm::estep_fused_lds2_kernel, dim3((uint32_t)nblk),
-                     dim3(kNT), lds, stream(),
-                     reinterpret_cast<const __hip_bfloat16*>(z.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(mfac.data_ptr()),
-                     add.data_ptr<float>(), w_out.data_ptr<float>(),
-                     partial.data_ptr<float>(), d, k, n, vec4);
-  HIP_CHECK(hipGetLastError());
+  launch_fused_lds<gmm::FacB16>("estep_fused_lds",
+                                gmm::estep_fused_lds_kernel, z, mfac, add,
+                                w_out, partial);
 }
 
 void estep_fused_f32_lds(torch::Tensor z, torch::Tensor mfac32,
                          torch::Tensor add, torch::Tensor w_out,
                          torch::Tensor partial) {
-  check_f32(z, "z");
-  check_f32(mfac32, "mfac32");
-  check_f32(add, "add");
-  check_f32(w_out, "w_out");
-  check_f32(partial, "partial");
-  const int d = (int)z.size(0);
-  const int64_t n = z.size(1);
-  const int k = (int)add.size(0);
-  TORCH_CHECK(d <= 31, "estep_fused_f32_lds needs D <= 31");
-  TORCH_CHECK(mfac32.numel() >= (int64_t)k * 32 * 32, "mfac32 too small");
-  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
-  const int64_t nblk = (n + 128 - 1) / 128;
-  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
-  const size_t lds =
-      sizeof(float) * ((size_t)128 * 33 + (size_t)k * (128 + 4));
-  TORCH_CHECK(lds <= 64 * 1024, "estep_fused_f32_lds LDS budget exceeded");
-  hipLaunchKernelGGL(gmm::estep_fused_f32_lds_kernel, dim3((uint32_t)nblk),
-                     dim3(kNT), lds, stream(), z.data_ptr<float>(),
-                     mfac32.data_ptr<float>(), add.data_ptr<float>(),
-                     w_out.data_ptr<float>(), partial.data_ptr<float>(), d,
-                     k, n);
+  launch_fused_lds<gmm::FacF32>("estep_fused_f32_lds",
+                                gmm::estep_fused_f32_lds_kernel, z, mfac32,
+                                add, w_out, partial);
+}
+
+// Same contract and LDS budget as estep_fused_lds; the default small-K path.
+void estep_fused_lds2(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
+                      torch::Tensor w_out, torch::Tensor partial) {
+  const char* name = "estep_fused_lds2";
+  const FusedShape s = check_fused<gmm::FacB16>(name, z, mfac, add, w_out,
+                                                partial, gmm::ESTL_BE);
+  // 16-byte posterior stores need every row start 16-byte aligned
+  const int vec4 = s.n % 4 == 0 &&
+                   reinterpret_cast<uintptr_t>(w_out.data_ptr()) % 16 == 0;
+  const size_t lds = fused_lds_budget<gmm::FacB16>(name, s.k);
+  hipLaunchKernelGGL(gmm::estep_fused_lds2_kernel, dim3((uint32_t)s.nblk),
+                     dim3(kNT), lds, stream(), data_as<__hip_bfloat16>(z),
+                     data_as<__hip_bfloat16>(mfac), add.data_ptr<float>(),
+                     w_out.data_ptr<float>(), partial.data_ptr<float>(), s.d,
+                     s.k, s.n, vec4);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -521,9 +522,8 @@ void estep_logw_big(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
   const int k = (int)add.size(0);
   TORCH_CHECK(d >= 1 && d <= 142, "estep_logw_big supports D <= 143");
   TORCH_CHECK(logw.size(0) == k && logw.size(1) == n, "logw shape");
-  const int kct =
-      d + 1 <= 32 ? 2 : d + 1 <= 48 ? 3 : d + 1 <= 80 ? 5 : 9;
-  const int rows = ((d + 31) / 32) * 32;
+  const int kct = gmm::mfac_kct(d);
+  const int rows = gmm::mfac_rows(d);
   const int rt_n = rows / 32;
   const int arow = kct * 16 + 8;
   // 256-event tiles where the LDS fits (gfx950: 160 KB/workgroup max),
@@ -587,9 +587,8 @@ void estep_logw_big_f32(torch::Tensor z, torch::Tensor mfac32,
   const int k = (int)add.size(0);
   TORCH_CHECK(d >= 1 && d <= 142, "estep_logw_big_f32 supports D <= 143");
   TORCH_CHECK(logw.size(0) == k && logw.size(1) == n, "logw shape");
-  const int kct =
-      d + 1 <= 32 ? 2 : d + 1 <= 48 ? 3 : d + 1 <= 80 ? 5 : 9;
-  const int rows = ((d + 31) / 32) * 32;
+  const int kct = gmm::mfac_kct(d);
+  const int rows = gmm::mfac_rows(d);
   TORCH_CHECK(mfac32.numel() >= (int64_t)k * rows * kct * 16,
               "mfac32 too small for big-D layout");
   const size_t lds = sizeof(float) * (size_t)128 * (kct * 16 + 4);
@@ -781,34 +780,6 @@ void emit_factors(torch::Tensor r, torch::Tensor means,
   hipLaunchKernelGGL(gmm::emit_mfac_from_r_kernel, dim3(k), dim3(kNT),
                      lds, stream(), r.data_ptr<float>(),
                      means.data_ptr<float>(), mp, mp32, d, pip, cst, addp);
-  HIP_CHECK(hipGetLastError());
-}
-
-void estep_fused_f32(torch::Tensor z, torch::Tensor mfac32,
-                     torch::Tensor add, torch::Tensor w_out,
-                     torch::Tensor lse_out, torch::Tensor partial) {
-  check_f32(z, "z");
-  check_f32(mfac32, "mfac32");
-  check_f32(add, "add");
-  check_f32(w_out, "w_out");
-  check_f32(partial, "partial");
-  const int d = (int)z.size(0);
-  const int64_t n = z.size(1);
-  const int k = (int)add.size(0);
-  TORCH_CHECK(d <= 31, "estep_fused_f32 needs D <= 31");
-  TORCH_CHECK(mfac32.numel() >= (int64_t)k * 32 * 32, "mfac32 too small");
-  TORCH_CHECK(w_out.size(0) == k && w_out.size(1) == n, "w_out shape");
-  const int64_t nblk = (n + 256 - 1) / 256;
-  TORCH_CHECK(partial.size(0) >= nblk, "partial buffer too small");
-  const size_t lds =
-      sizeof(float) * ((size_t)256 * 33 + 2 * (256 / 64) * 256 + 256);
-  check_f32(lse_out, "lse_out");
-  TORCH_CHECK(lse_out.numel() == n, "lse_out must be [N]");
-  hipLaunchKernelGGL(gmm::estep_fused_f32_kernel, dim3((uint32_t)nblk),
-                     dim3(kNT), lds, stream(), z.data_ptr<float>(),
-                     mfac32.data_ptr<float>(), add.data_ptr<float>(),
-                     w_out.data_ptr<float>(), lse_out.data_ptr<float>(),
-                     partial.data_ptr<float>(), d, k, n);
   HIP_CHECK(hipGetLastError());
 }
 
