@@ -257,20 +257,24 @@ class EmEngine:
                 if self.mfac32 is not None:
                     w, lik = F.estep_fused_f32_lds(self.x_estep,
                                                    self.mfac32[:k], add,
-                                                   self.w[:k], need_lik)
+                                                   self.w[:k], need_lik,
+                                                   lik_out=self._lik_dev)
                 else:
                     w, lik = F.estep_fused_lds(self.x_estep, self.mfac[:k],
-                                               add, self.w[:k], need_lik)
+                                               add, self.w[:k], need_lik,
+                                               lik_out=self._lik_dev)
             elif self.use_fused_estep:
                 self._w_is_logw = True
                 add = self._add[:k]
                 if self.mfac32 is not None:
                     w, lik = F.estep_fused_f32(self.x_estep, self.mfac32[:k],
                                                add, self.w[:k], self._lse,
-                                               need_lik)
+                                               need_lik,
+                                               lik_out=self._lik_dev)
                 else:
                     w, lik = F.estep_fused(self.x_estep, self.mfac[:k], add,
-                                           self.w[:k], self._lse, need_lik)
+                                           self.w[:k], self._lse, need_lik,
+                                           lik_out=self._lik_dev)
             elif self.use_big_estep:
                 add = self._add[:k]
                 if self.mfac32 is not None:
@@ -281,14 +285,16 @@ class EmEngine:
                 else:
                     logw = F.estep_logw_big(self.x_estep, self.mfac[:k],
                                             add, self.w[:k])
-                lik = F.estep_lse(logw, self._lse, need_lik)
+                lik = F.estep_lse(logw, self._lse, need_lik,
+                                  lik_out=self._lik_dev)
                 self._w_is_logw = True
             elif self.device.type == "cuda":
                 logw = F.estep_logw(
                     self.x_estep, st.means, st.Rinv, st.constant, st.pi,
                     self.cfg.diag_only, out=self.w[:k],
                 )
-                lik = F.estep_lse(logw, self._lse, need_lik)
+                lik = F.estep_lse(logw, self._lse, need_lik,
+                                  lik_out=self._lik_dev)
                 self._w_is_logw = True
             else:
                 logw = F.estep_logw(
@@ -301,11 +307,14 @@ class EmEngine:
 
     def _finish_likelihood(self, lik_part: torch.Tensor) -> None:
         """All-reduce the shard likelihood into the persistent device
-        scalar (graph-capturable: no host sync)."""
+        scalar (graph-capturable: no host sync). The GPU E-steps reduce
+        straight into that scalar, so there it is reduced in place and
+        nothing is copied."""
         with self.profile.time("comm"):
             t = lik_part.reshape(1)
             pdist.all_reduce_(t)
-            self._lik_dev.copy_(t)
+            if t.data_ptr() != self._lik_dev.data_ptr():
+                self._lik_dev.copy_(t)
 
     def _reduce_likelihood(self, lik_part: torch.Tensor) -> float:
         self._finish_likelihood(lik_part)

@@ -51,8 +51,10 @@ def estep_posteriors(logw: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 
 
 def estep_lse(logw: torch.Tensor, lse: torch.Tensor,
-              need_lik: bool = True) -> torch.Tensor | None:
-    """Per-event log-sum-exp into lse [N] + likelihood scalar (CUDA).
+              need_lik: bool = True,
+              lik_out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """Per-event log-sum-exp into lse [N] + likelihood scalar (CUDA),
+    reduced into ``lik_out`` [1] when one is given.
 
     logw is NOT normalized — the lse-aware M-step kernels apply
     exp(logw - lse) while staging w, deleting the posterior write+read
@@ -62,7 +64,8 @@ def estep_lse(logw: torch.Tensor, lse: torch.Tensor,
     hip_ext().estep_lse(logw, lse, partial)
     if not need_lik:
         return None
-    lik = torch.empty(1, dtype=torch.float32, device=logw.device)
+    lik = (lik_out if lik_out is not None
+           else torch.empty(1, dtype=torch.float32, device=logw.device))
     hip_ext().reduce_scalar(partial, lik)
     return lik
 
@@ -229,9 +232,11 @@ def constants(r: torch.Tensor, means: torch.Tensor | None = None,
 
 def _run_fused(entry: str, tile: int, z: torch.Tensor, fac: torch.Tensor,
                add: torch.Tensor, w_out: torch.Tensor, need_lik: bool,
-               *lse: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor | None]:
+               *lse: torch.Tensor, lik_out: torch.Tensor | None = None
+               ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """Launch one fused E-step entry point (`tile` events per block) and
-    reduce its per-block likelihood partials."""
+    reduce its per-block likelihood partials, into `lik_out` [1] when the
+    caller has a place for the scalar (saves it a device copy)."""
     ext = hip_ext()
     nblk = (z.shape[1] + tile - 1) // tile
     # every launched block writes its partial slot: no zero-fill needed
@@ -239,20 +244,22 @@ def _run_fused(entry: str, tile: int, z: torch.Tensor, fac: torch.Tensor,
     getattr(ext, entry)(z, fac, add, w_out, *lse, partial)
     if not need_lik:
         return w_out, None
-    lik = torch.empty(1, dtype=torch.float32, device=z.device)
+    lik = (lik_out if lik_out is not None
+           else torch.empty(1, dtype=torch.float32, device=z.device))
     ext.reduce_scalar(partial, lik)
     return w_out, lik
 
 
 def estep_fused(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
                 w_out: torch.Tensor, lse: torch.Tensor,
-                need_lik: bool = True
+                need_lik: bool = True, lik_out: torch.Tensor | None = None
                 ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """Fused bf16-MFMA E-step (CUDA only): LOG weights into w_out [K,N],
     per-event log-sum-exp into lse [N], returns (w_out, likelihood).
     Online-softmax over 256-event blocks; the lse-aware M-step applies
     exp(w_out - lse) on the fly — posteriors are never materialized."""
-    return _run_fused("estep_fused", 256, z, mfac, add, w_out, need_lik, lse)
+    return _run_fused("estep_fused", 256, z, mfac, add, w_out, need_lik, lse,
+                      lik_out=lik_out)
 
 
 def estep_fused_available(device: torch.device, dtype: str, d: int,
@@ -275,33 +282,36 @@ def estep_fused_lds_available(device: torch.device, dtype: str, d: int,
 
 
 def estep_fused_lds(z: torch.Tensor, mfac: torch.Tensor, add: torch.Tensor,
-                    w_out: torch.Tensor, need_lik: bool = True
+                    w_out: torch.Tensor, need_lik: bool = True,
+                    lik_out: torch.Tensor | None = None
                     ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """v1 fused bf16 E-step: POSTERIORS into w_out, likelihood scalar."""
     # GMM_ESTEP_LDS=legacy selects the first version of the kernel
     # (same-build A/B); the log-weights of the two are bitwise equal
     legacy = os.environ.get("GMM_ESTEP_LDS", "lds2") == "legacy"
     return _run_fused("estep_fused_lds" if legacy else "estep_fused_lds2",
-                      128, z, mfac, add, w_out, need_lik)
+                      128, z, mfac, add, w_out, need_lik, lik_out=lik_out)
 
 
 def estep_fused_f32_lds(z: torch.Tensor, mfac32: torch.Tensor,
                         add: torch.Tensor, w_out: torch.Tensor,
-                        need_lik: bool = True
+                        need_lik: bool = True,
+                        lik_out: torch.Tensor | None = None
                         ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """v1 exact-f32 fused E-step: POSTERIORS into w_out."""
     return _run_fused("estep_fused_f32_lds", 128, z, mfac32, add, w_out,
-                      need_lik)
+                      need_lik, lik_out=lik_out)
 
 
 def estep_fused_f32(z: torch.Tensor, mfac32: torch.Tensor, add: torch.Tensor,
                     w_out: torch.Tensor, lse: torch.Tensor,
-                    need_lik: bool = True
+                    need_lik: bool = True,
+                    lik_out: torch.Tensor | None = None
                     ) -> tuple[torch.Tensor, torch.Tensor | None]:
     """Exact-f32 MFMA fused E-step (CUDA, D <= 31, any K): log weights
     into w_out, per-event log-sum-exp into lse."""
     return _run_fused("estep_fused_f32", 256, z, mfac32, add, w_out,
-                      need_lik, lse)
+                      need_lik, lse, lik_out=lik_out)
 
 
 def estep_big_available(device: torch.device, dtype: str, d: int) -> bool:

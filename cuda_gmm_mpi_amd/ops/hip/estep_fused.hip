@@ -74,11 +74,16 @@ constexpr int z_tile_floats() {
   return BE * Fac::ZROW * (int)sizeof(typename Fac::Z) / 4;
 }
 
-// ||y||^2 of the 16 accumulator rows this lane holds, as one fmaf chain
+// ||y||^2 of the accumulator rows this lane holds, as one fmaf chain over
+// the first NL registers. Register r holds Y row (r & 3) + 8 (r >> 2) +
+// 4 (lane >> 5) and the factor table is exactly zero from row d on, so with
+// NL = 4 ceil(d / 8) the registers left out are +0 in every lane and
+// fmaf(0, 0, s) == s: the sum is bitwise the 16-register one.
+template <int NL>
 __device__ __forceinline__ float sqnorm(const f32x16_t& y) {
   float s = 0.0f;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) s = fmaf(y[r], y[r], s);
+  for (int r = 0; r < NL; ++r) s = fmaf(y[r], y[r], s);
   return s;
 }
 
@@ -653,6 +658,7 @@ estep_fused_f32_lds_kernel(const float* __restrict__ z,
 // ---------------------------------------------------------------------------
 constexpr int ESTL2_NS = 8;  // cluster slices in pass 2 (NT / 32)
 
+template <int NL>  // live accumulator registers, 4 ceil(d / 8): see sqnorm
 __global__ void __launch_bounds__(NT, 3)
 estep_fused_lds2_kernel(const __hip_bfloat16* __restrict__ z,
                         const __hip_bfloat16* __restrict__ mfac,
@@ -750,7 +756,7 @@ estep_fused_lds2_kernel(const __hip_bfloat16* __restrict__ z,
       y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l1, b1[t], y[t], 0, 0, 0);
     float s[ESTL_BE / 32];
 #pragma unroll
-    for (int t = 0; t < ESTL_BE / 32; ++t) s[t] = sqnorm(y[t]);
+    for (int t = 0; t < ESTL_BE / 32; ++t) s[t] = sqnorm<NL>(y[t]);
     // the 32 Y rows live across the two lane halves. Swap the upper half of
     // tile t with the lower half of tile t+1: lanes 0-31 then hold both
     // halves of tile t, lanes 32-63 both of tile t+1 (lower half first in

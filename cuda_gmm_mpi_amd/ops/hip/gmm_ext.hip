@@ -190,6 +190,19 @@ void mstep_covariance_partials(torch::Tensor x, torch::Tensor w,
   }
 }
 
+// The factor emission gives thread i row i of the factorization and stores
+// 8 cells at a time: D within one block, 16-byte aligned factor tables.
+void check_factor_out(const torch::Tensor& mfac, const torch::Tensor& mfac32,
+                      int d) {
+  TORCH_CHECK(d <= kNT, "factor emission needs D <= ", kNT);
+  TORCH_CHECK(mfac.numel() == 0 ||
+                  reinterpret_cast<uintptr_t>(mfac.data_ptr()) % 16 == 0,
+              "mfac must be 16-byte aligned");
+  TORCH_CHECK(mfac32.numel() == 0 ||
+                  reinterpret_cast<uintptr_t>(mfac32.data_ptr()) % 16 == 0,
+              "mfac32 must be 16-byte aligned");
+}
+
 void constants(torch::Tensor r, torch::Tensor means, torch::Tensor pi,
                torch::Tensor rinv, torch::Tensor logdet,
                torch::Tensor constant, torch::Tensor add, torch::Tensor mfac,
@@ -218,6 +231,7 @@ void constants(torch::Tensor r, torch::Tensor means, torch::Tensor pi,
                     d <= 142,
                 "mfac must be bf16 [K,2,RT*32,KCT*16] with D <= 142");
     mp = reinterpret_cast<__hip_bfloat16*>(mfac.data_ptr());
+    check_factor_out(mfac, mfac32, d);
   }
   auto s = stream();
   float* pip = pi.numel() > 0 ? pi.data_ptr<float>() : nullptr;
@@ -501,11 +515,21 @@ void estep_fused_lds2(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
   const int vec4 = s.n % 4 == 0 &&
                    reinterpret_cast<uintptr_t>(w_out.data_ptr()) % 16 == 0;
   const size_t lds = fused_lds_budget<gmm::FacB16>(name, s.k);
-  hipLaunchKernelGGL(gmm::estep_fused_lds2_kernel, dim3((uint32_t)s.nblk),
-                     dim3(kNT), lds, stream(), data_as<__hip_bfloat16>(z),
-                     data_as<__hip_bfloat16>(mfac), add.data_ptr<float>(),
-                     w_out.data_ptr<float>(), partial.data_ptr<float>(), s.d,
-                     s.k, s.n, vec4);
+  // the kernel sums only the accumulator registers that hold factor rows
+  // below d (groups of 8 rows): chosen here, so its cluster loop has no
+  // branch on it
+#define LAUNCH_LDS2(NL)                                                      \
+  hipLaunchKernelGGL(gmm::estep_fused_lds2_kernel<NL>,                       \
+                     dim3((uint32_t)s.nblk), dim3(kNT), lds, stream(),       \
+                     data_as<__hip_bfloat16>(z),                             \
+                     data_as<__hip_bfloat16>(mfac), add.data_ptr<float>(),   \
+                     w_out.data_ptr<float>(), partial.data_ptr<float>(),     \
+                     s.d, s.k, s.n, vec4)
+  if (s.d <= 8) LAUNCH_LDS2(4);
+  else if (s.d <= 16) LAUNCH_LDS2(8);
+  else if (s.d <= 24) LAUNCH_LDS2(12);
+  else LAUNCH_LDS2(16);
+#undef LAUNCH_LDS2
   HIP_CHECK(hipGetLastError());
 }
 
@@ -665,8 +689,12 @@ void reduce_chunks(torch::Tensor partials, torch::Tensor out) {
   const int c = (int)partials.size(0);
   const int64_t m = partials.numel() / c;
   TORCH_CHECK(out.numel() == m, "out shape");
-  const int grid = (int)std::min<int64_t>((m + kNT - 1) / kNT, 4096);
-  hipLaunchKernelGGL(gmm::reduce_chunks_kernel, dim3(grid), dim3(kNT), 0,
+  // a column per thread, one wave per block: ~20k columns at the flagship
+  // shape make 325 blocks over the 256 CUs (82 four-wave blocks left two
+  // thirds of them idle in a kernel that lives on loads in flight)
+  constexpr int kRcNT = 64;
+  const int grid = (int)std::min<int64_t>((m + kRcNT - 1) / kRcNT, 8192);
+  hipLaunchKernelGGL(gmm::reduce_chunks_kernel, dim3(grid), dim3(kRcNT), 0,
                      stream(), partials.data_ptr<float>(),
                      out.data_ptr<float>(), c, m);
   HIP_CHECK(hipGetLastError());
@@ -733,6 +761,7 @@ void mstep_finalize_emit(torch::Tensor packed, torch::Tensor avgvar,
     check_f32(mfac32, "mfac32");
     mp32 = mfac32.data_ptr<float>();
   }
+  check_factor_out(mfac, mfac32, d);
   const size_t lds = sizeof(float) * (2 * (size_t)d * (d | 1) + d);
   if (lds > 64 * 1024) {
     HIP_CHECK(hipFuncSetAttribute(
@@ -767,6 +796,7 @@ void emit_factors(torch::Tensor r, torch::Tensor means,
     check_f32(mfac32, "mfac32");
     mp32 = mfac32.data_ptr<float>();
   }
+  check_factor_out(mfac, mfac32, d);
   const size_t lds = sizeof(float) * (2 * (size_t)d * (d | 1) + d);
   if (lds > 64 * 1024) {
     HIP_CHECK(hipFuncSetAttribute(

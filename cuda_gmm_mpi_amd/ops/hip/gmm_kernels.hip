@@ -251,18 +251,30 @@ estep_lse_kernel(const float* __restrict__ logw, float* __restrict__ lse,
 
 // Deterministic chunk reduction: out[j] = sum_i in[i*m + j] (fixed i
 // order). Replaces torch's generic reduce_kernel (19.6 us for the
-// [256, K*Pp] moments partials; this is bandwidth-bound ~4 us).
+// [256, K*Pp] moments partials).
 __global__ void __launch_bounds__(NT)
 reduce_chunks_kernel(const float* __restrict__ in, float* __restrict__ out,
                      int c, int64_t m) {
-  // 8 independent accumulators: m is only ~20k columns (82 blocks), so
-  // without ILP the chunk loop serializes on L2 latency (measured 78 us
-  // vs torch's 19; this form is ~bandwidth-bound). The reassociation is
-  // FIXED (same order every run): still bitwise deterministic.
-  for (int64_t j = (int64_t)blockIdx.x * NT + threadIdx.x; j < m;
-       j += (int64_t)gridDim.x * NT) {
+  // 8 independent accumulators: m is only ~20k columns, so without ILP the
+  // chunk loop serializes on memory latency (measured 78 us vs torch's
+  // 19). The reassociation is FIXED (same order every run): acc[u] takes
+  // chunks i == u (mod 8) in ascending order, then the tree below. The
+  // main loop only puts 32 loads in flight before the first add (8 left
+  // the kernel at 32 dependent round trips, 12.8 us for 21 MB); the adds
+  // keep that order. One-wave blocks spread the columns over every CU.
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m;
+       j += (int64_t)gridDim.x * blockDim.x) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int i = 0;
+    for (; i + 32 <= c; i += 32) {
+      float v[32];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) v[u] = in[(int64_t)(i + u) * m + j];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] += v[8 * q + u];
+    }
     for (; i + 8 <= c; i += 8) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) acc[u] += in[(int64_t)(i + u) * m + j];
@@ -278,8 +290,22 @@ reduce_chunks_kernel(const float* __restrict__ in, float* __restrict__ out,
 __global__ void __launch_bounds__(NT)
 reduce_scalar_kernel(const float* __restrict__ in, float* __restrict__ out,
                      int64_t n) {
+  // each lane adds in[tid], in[tid + NT], ... in that order; the loads of
+  // 16 terms are issued together so the chain is not one memory round
+  // trip per term (31 of them at the flagship's 7813 partials)
+  constexpr int U = 16;
   float acc = 0.0f;
-  for (int64_t i = threadIdx.x; i < n; i += NT) acc += in[i];
+  for (int64_t i = threadIdx.x; i < n; i += (int64_t)U * NT) {
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t idx = i + (int64_t)u * NT;
+      v[u] = in[idx < n ? idx : i];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + (int64_t)u * NT < n) acc += v[u];
+  }
   __shared__ float wsum[NT / WAVE];
   for (int off = WAVE / 2; off > 0; off >>= 1)
     acc += __shfl_down(acc, off, WAVE);
@@ -460,9 +486,22 @@ mstep_finalize_kernel(const float* __restrict__ packed,
 // LU inverse of an ill-conditioned R loses positive-definiteness and
 // clamped pivots cascade into ~1e15-scale factor rows whose quadratic
 // forms overflow fp32 (K >> N/D regimes).
-// `a` is scratch LDS holding R [d*d] (becomes L, then F in place);
-// `o` [d*d] is the snapshot for the cross-thread triangular inversion;
-// u0 [d] follows o.
+// acc - round(x * y): the empty asm makes the product a value of its own,
+// so the compiler cannot contract the pair into one fused multiply-add.
+__device__ __forceinline__ float unfused_mulsub(float acc, float x, float y) {
+  float p = x * y;
+  asm("" : "+v"(p));
+  return acc - p;
+}
+
+// `a` is scratch LDS [d*ldp] for R, factored in place into L (only the
+// lower triangle is read); with r_global == nullptr the caller has put R
+// there already, barrier included. `o` [d*ldp] receives F (lower triangle
+// only); u0 [d] follows o. Thread i owns row i of L and column i of F, so
+// d <= blockDim.x (the launchers check it; LDS stops at D = 142 anyway).
+// Every element keeps the operations and the kk-ascending order of the
+// straightforward column Cholesky / forward substitution; what changed is
+// who computes them and how often the block meets at a barrier.
 __device__ inline void emit_mfac(float* a, float* o,
                                  const float* __restrict__ r_global,
                                  const float* __restrict__ means,
@@ -476,26 +515,41 @@ __device__ inline void emit_mfac(float* a, float* o,
   // whole lane groups on one bank (8-way at d = 24)
   const int ldp = d | 1;
   float* u0 = o + d * ldp;
-  for (int t = tid; t < d * d; t += blockDim.x)
-    a[(t / d) * ldp + t % d] = r_global[(int64_t)c * d * d + t];
-  __syncthreads();
-  // in-place lower Cholesky of R (column j: pivot, then rows below)
-  for (int j = 0; j < d; ++j) {
-    if (tid == 0) {
-      const float diag0 = fabsf(a[j * ldp + j]);
-      float s = a[j * ldp + j];
-      for (int kk = 0; kk < j; ++kk) s -= a[j * ldp + kk] * a[j * ldp + kk];
-      a[j * ldp + j] = sqrtf(fmaxf(s, 1e-8f * diag0 + 1e-30f));
-    }
+  if (r_global != nullptr) {
+    for (int t = tid; t < d * d; t += blockDim.x)
+      a[(t / d) * ldp + t % d] = r_global[(int64_t)c * d * d + t];
     __syncthreads();
-    const float piv = a[j * ldp + j];
-    for (int i = j + 1 + tid; i < d; i += blockDim.x) {
-      float s = a[i * ldp + j];
+  }
+  // in-place lower Cholesky of R, one barrier per column. The pivot of
+  // row i is R[i][i] - sum_kk L[i][kk]^2 in kk order: the row's owner
+  // keeps that running sum in a register, subtracts each L[i][j] as it
+  // produces it, and publishes the pivot together with L[i][i-1], one
+  // column step before anyone reads it (a lone thread used to walk the
+  // row through LDS for every pivot, between two barriers of its own).
+  {
+    const bool own = tid < d;
+    float* ri = a + tid * ldp;
+    float sd = 0.0f, diag0 = 0.0f;
+    if (own) {
+      sd = ri[tid];
+      diag0 = fabsf(sd);
+    }
+    if (tid == 0) ri[0] = sqrtf(fmaxf(sd, fmaf(1e-8f, diag0, 1e-30f)));
+    __syncthreads();
+    for (int j = 0; j + 1 < d; ++j) {
+      if (own && tid > j) {
+        const float* rj = a + j * ldp;
+        float s = ri[j];
 #pragma unroll 8
-      for (int kk = 0; kk < j; ++kk) s -= a[i * ldp + kk] * a[j * ldp + kk];
-      a[i * ldp + j] = s / piv;
+        for (int kk = 0; kk < j; ++kk) s = fmaf(-ri[kk], rj[kk], s);
+        const float l = s / rj[j];
+        ri[j] = l;
+        sd = fmaf(-l, l, sd);
+        if (tid == j + 1)
+          ri[tid] = sqrtf(fmaxf(sd, fmaf(1e-8f, diag0, 1e-30f)));
+      }
+      __syncthreads();
     }
-    __syncthreads();
   }
   // ln|R| = 2 sum ln diag(L): lets the EM iteration skip the LU kernel
   // entirely on the factor paths (constant = -D/2 ln 2pi - 0.5 ln|R|,
@@ -521,52 +575,94 @@ __device__ inline void emit_mfac(float* a, float* o,
     }
     __syncthreads();
   }
-  // snapshot L, then invert in place: F = L^-1 (lower). Thread i owns
-  // column i (serial down rows); cross-column L reads come from the
-  // snapshot, this thread's own F values from a.
-  for (int t = tid; t < d * ldp; t += blockDim.x) o[t] = a[t];
-  __syncthreads();
-  for (int i = tid; i < d; i += blockDim.x) {
+  // F = L^-1 (lower) by forward substitution, L read from a and F written
+  // to o (no snapshot copy: nothing is overwritten). Thread i owns column
+  // i, serial down the rows; its own earlier F values come back from o.
+  // The sum runs in kk order with the rounding the kernel has always had:
+  // the first (j - i) % 8 terms as fused multiply-adds, the rest in eights
+  // as a rounded product subtracted (unfused_mulsub keeps it that way).
+  if (tid < d) {
+    const int i = tid;
     for (int j = i; j < d; ++j) {
+      const float* lj = a + j * ldp;
       float xv = 1.0f;
       if (i != j) {
         xv = 0.0f;
-#pragma unroll 8
-        for (int kk = i; kk < j; ++kk)
-          xv -= o[j * ldp + kk] * a[kk * ldp + i];
+        int kk = i;
+        for (const int head = i + ((j - i) & 7); kk < head; ++kk)
+          xv = fmaf(-lj[kk], o[kk * ldp + i], xv);
+        for (; kk < j; kk += 8) {
+          float lv[8], fv[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            lv[u] = lj[kk + u];
+            fv[u] = o[(kk + u) * ldp + i];
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u) xv = unfused_mulsub(xv, lv[u], fv[u]);
+        }
       }
-      a[j * ldp + i] = xv / o[j * ldp + j];
+      o[j * ldp + i] = xv / lj[j];
     }
   }
   __syncthreads();
   // u0 = -F mu (mu = centered cluster means; F lower: j <= i)
-  for (int i = tid; i < d; i += blockDim.x) {
+  if (tid < d) {
+    const float* fi = o + tid * ldp;
     float s = 0.0f;
 #pragma unroll 8
-    for (int j = 0; j <= i; ++j) s += a[i * ldp + j] * means[c * d + j];
-    u0[i] = -s;
+    for (int j = 0; j <= tid; ++j) s = fmaf(fi[j], means[c * d + j], s);
+    u0[tid] = -s;
   }
   __syncthreads();
   // write hi/lo bf16 fragments: rows padded to RT*32, k-slots to KC*16
   // (RT = ceil(d/32) row-tiles, KC = ceil((d+1)/16) MFMA k-chunks; for
   // d <= 31 this is the original [32][32] layout). k-order is contiguous
-  // (identity fragment map, hardware-verified by the probes).
+  // (identity fragment map, hardware-verified by the probes). A work item
+  // is 8 consecutive k-slots of one row (cols is a multiple of 16): built
+  // in registers, stored as 16 bytes per bf16 plane and 32 bytes of fp32.
   const int rows = mfac_rows(d);
   const int cols = mfac_kct(d) * 16;
   const int cells = rows * cols;
+  const int cpr = cols >> 3;  // items per row
   __hip_bfloat16* out = mfac + (int64_t)c * 2 * cells;
   float* out32 = mfac32 ? mfac32 + (int64_t)c * cells : nullptr;
-  for (int t = tid; t < cells; t += blockDim.x) {
-    const int i = t / cols, kx = t % cols;
-    float v = 0.0f;
-    if (i < d) {
-      if (kx < d) v = (kx <= i) ? a[i * ldp + kx] : 0.0f;
-      else if (kx == d) v = u0[i];
+  for (int g = tid; g < rows * cpr; g += blockDim.x) {
+    const int i = g / cpr, kx0 = (g - i * cpr) << 3;
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = 0.0f;
+    if (i < d && kx0 <= d) {
+      const float* fi = o + i * ldp;
+      const float ui = u0[i];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int kx = kx0 + u;
+        // clamped address: the row's slots past the diagonal are not F
+        const float f = fi[min(kx, i)];
+        v[u] = (kx <= i) ? f : ((kx == d) ? ui : 0.0f);
+      }
     }
-    const __hip_bfloat16 hi = __float2bfloat16(v);
-    out[t] = hi;
-    out[cells + t] = __float2bfloat16(v - __bfloat162float(hi));
-    if (out32) out32[t] = v;
+    unsigned int ph[4], pl[4];
+#pragma unroll
+    for (int u = 0; u < 8; u += 2) {
+      const __hip_bfloat16 h0 = __float2bfloat16(v[u]);
+      const __hip_bfloat16 h1 = __float2bfloat16(v[u + 1]);
+      const __hip_bfloat16 l0 = __float2bfloat16(v[u] - __bfloat162float(h0));
+      const __hip_bfloat16 l1 =
+          __float2bfloat16(v[u + 1] - __bfloat162float(h1));
+      ph[u >> 1] = (unsigned int)__bfloat16_as_ushort(h0) |
+                   ((unsigned int)__bfloat16_as_ushort(h1) << 16);
+      pl[u >> 1] = (unsigned int)__bfloat16_as_ushort(l0) |
+                   ((unsigned int)__bfloat16_as_ushort(l1) << 16);
+    }
+    const int t = g << 3;
+    *(uint4*)(out + t) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
+    *(uint4*)(out + cells + t) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+    if (out32) {
+      *(float4*)(out32 + t) = make_float4(v[0], v[1], v[2], v[3]);
+      *(float4*)(out32 + t + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
   }
 }
 
@@ -600,11 +696,29 @@ mstep_finalize_emit_kernel(const float* __restrict__ packed,
   const bool ge1 = n_c >= 1.0f;
   const bool gt05 = n_c > 0.5f;
 
-  if (threadIdx.x == 0) {
-    n_out[c] = n_c;
+  if (threadIdx.x < WAVE) {
+    // pi denominator: sum of all N in cluster order, one fp32 accumulator.
+    // Wave 0 loads 64 of them at a time, a lane each, and adds them lane
+    // by lane (a single thread walking k strided loads one after the
+    // other kept the other 255 waiting at the barrier below).
     float total = 0.0f;
-    for (int cc = 0; cc < k; ++cc) total += packed[(int64_t)cc * pp + pp - 1];
-    pi[c] = (n_c < 0.5f) ? 1e-10f : n_c / total;
+    for (int base = 0; base < k; base += WAVE) {
+      const int cc = min(base + (int)threadIdx.x, k - 1);
+      const int nv = __float_as_int(packed[(int64_t)cc * pp + pp - 1]);
+      const int cnt = min(WAVE, k - base);
+      if (cnt == WAVE) {
+#pragma unroll
+        for (int l = 0; l < WAVE; ++l)
+          total += __int_as_float(__builtin_amdgcn_readlane(nv, l));
+      } else {
+        for (int l = 0; l < cnt; ++l)
+          total += __int_as_float(__builtin_amdgcn_readlane(nv, l));
+      }
+    }
+    if (threadIdx.x == 0) {
+      n_out[c] = n_c;
+      pi[c] = (n_c < 0.5f) ? 1e-10f : n_c / total;
+    }
   }
   for (int i = threadIdx.x; i < d; i += NT) {
     const float m = gt05 ? row[p + i] / n_c : 0.0f;
@@ -616,18 +730,21 @@ mstep_finalize_emit_kernel(const float* __restrict__ packed,
   for (int t = threadIdx.x; t < p; t += NT) {
     int i, j;
     tri_row_col(t, &i, &j);
-    float cov = ge1 ? row[t] - n_c * mu[i] * mu[j] : 0.0f;
+    // (n_c mu_i) rounded, then one fused multiply-add, as compiled so far
+    float cov = ge1 ? fmaf(-(n_c * mu[i]), mu[j], row[t]) : 0.0f;
     if (i == j) cov += reg;
     float rv;
     if (gt05) rv = cov / n_c;
     else rv = (i == j) ? 1.0f : 0.0f;
     r_out[((int64_t)c * d + i) * d + j] = rv;
     if (i != j) r_out[((int64_t)c * d + j) * d + i] = rv;
+    a[i * ldp + j] = rv;  // the factorization reads the lower triangle only
   }
   __syncthreads();
-  // R written by THIS block is L1-visible after the barrier; the
-  // emission path reloads it (and means) through the same pointers
-  emit_mfac(a, o, r_out, means, mfac, mfac32, c, d, pi, constant, add);
+  // R is already where the factorization wants it (it used to be stored
+  // and read back through global memory); means are reloaded through the
+  // pointer this block has just written them to
+  emit_mfac(a, o, nullptr, means, mfac, mfac32, c, d, pi, constant, add);
 }
 
 // NOTE (negative result, round 2): a wave-per-cluster constants variant
