@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .engine import build_engine
+from .models.model import GmmModel
 from .parallel import dist as pdist
 from .utils import io as gio
 from .utils.config import GmmConfig, MAX_CLUSTERS
@@ -67,6 +68,10 @@ def make_parser() -> argparse.ArgumentParser:
                         "checkpoint there is resumed automatically")
     p.add_argument("--metrics-out", default=None,
                    help="write machine-readable run metrics (JSON) here")
+    p.add_argument("--save-model", default=None, metavar="PATH",
+                   help="save the fitted model as a .npz that "
+                        "`python -m cuda_gmm_mpi_amd.classify` scores new "
+                        "data with")
     p.add_argument("--gpus", type=int, default=None,
                    help="spawn N single-GPU worker processes on this node "
                         "(one rank per GPU over RCCL)")
@@ -106,7 +111,8 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                    device: str, write_results: bool = True,
                    profile_report: bool = False,
                    scatter_input: bool = False,
-                   striped_results: bool = False) -> dict:
+                   striped_results: bool = False,
+                   save_model: str | None = None) -> dict:
     """Full pipeline on already-initialized process group. Returns a result
     dict (rank 0) with num_clusters / rissanen / likelihood.
 
@@ -145,6 +151,12 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
     # state in place.
     out_state = result.state.to("cpu").clone(with_memberships=False)
     out_state.means += engine.center.cpu().unsqueeze(0)
+    # the model keeps the internal-frame means: scoring the training data
+    # with it then reproduces w_shard exactly
+    model = GmmModel.from_state(result.state.to("cpu"), engine.center.cpu(),
+                                cfg.diag_only, cfg.bug_compat)
+    if save_model and rank == 0:
+        model.save(save_model)
     memberships = None
     if striped_results:
         # SURVEY §5 long-context plan: per-rank file stripes — shard-local
@@ -178,6 +190,7 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
         "likelihood": result.likelihood,
         "rissanen_by_k": result.rissanen_by_k,
         "state": out_state,
+        "model": model,
         "memberships": memberships,
         "seconds": elapsed,
         "total_em_iterations": engine.total_em_iterations,
@@ -275,6 +288,7 @@ def main(argv=None) -> int:
             data, cfg, args.outfile, device,
             write_results=args.write_results, profile_report=args.profile,
             scatter_input=scatter, striped_results=args.striped_results,
+            save_model=args.save_model,
         )
         if rank == 0 and args.metrics_out:
             import json

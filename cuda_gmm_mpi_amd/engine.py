@@ -157,28 +157,11 @@ class EmEngine:
         merged cluster's constant comes from the host path and must feed
         the next E-step unchanged, but the factor tables
         must match the compacted state."""
-        if self.mfac is None and self.mfac32 is None:
-            return
-        from .ops.backend import hip_ext
         st = self.state.shrink(k)
-        r_src = st.R
-        if self.cfg.diag_only:
-            # DIAG parity through a merge: the reference's diag E-step
-            # reads diag(inv(R_merged_full)) — the host merge computed
-            # the FULL-matrix inverse and quirk #8 carries it into the
-            # next E-step — which is NOT inv(diag(R_full)). Emit the
-            # factors from the diagonal matrix with exactly that
-            # inverse; for an already-diagonal R (seed, resume, every
-            # iteration after the first M-step) this is identical to R.
-            d_inv = st.Rinv.diagonal(dim1=-2, dim2=-1)
-            r_src = torch.diag_embed(1.0 / d_inv)
-        empty_b = torch.empty(0, dtype=torch.bfloat16, device=self.device)
-        empty_f = torch.empty(0, dtype=torch.float32, device=self.device)
-        hip_ext().emit_factors(
-            r_src.contiguous(), st.means.contiguous(),
-            self.mfac[:k] if self.mfac is not None else empty_b,
-            self.mfac32[:k] if self.mfac32 is not None else empty_f,
-            empty_f, empty_f, empty_f,  # constants NOT recomputed (quirk #8)
+        F.emit_factor_tables(
+            st.R, st.Rinv, st.means, self.cfg.diag_only,
+            self.mfac[:k] if self.mfac is not None else None,
+            self.mfac32[:k] if self.mfac32 is not None else None,
         )
 
     def _update_constants(self, st: GmmState) -> None:
@@ -240,7 +223,7 @@ class EmEngine:
         resume) where constants must NOT be recomputed (quirk #8)."""
         if self._add is not None:
             st = self.state.shrink(k)
-            self._add[:k] = st.constant + torch.log(st.pi)
+            self._add[:k] = F.logw_offsets(st.constant, st.pi)
 
     # ------------------------------------------------------------------ EM
 

@@ -52,10 +52,35 @@ def estep_posteriors(logw: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     Returns (w [K, N] with columns summing to 1, likelihood scalar tensor).
     Log-sum-exp with per-event max for stability, like the reference.
     """
-    m = logw.max(dim=0).values  # [N]
-    denom = m + torch.log(torch.exp(logw - m.unsqueeze(0)).sum(dim=0))
+    denom = estep_lse(logw)
     w = torch.exp(logw - denom.unsqueeze(0))
     return w, denom.sum()
+
+
+def estep_lse(logw: torch.Tensor) -> torch.Tensor:
+    """Per-event log-sum-exp [N] of logw [K, N]: ln p(x_e)."""
+    m = logw.max(dim=0).values  # [N]
+    return m + torch.log(torch.exp(logw - m.unsqueeze(0)).sum(dim=0))
+
+
+def classify(x: torch.Tensor, means: torch.Tensor, rinv: torch.Tensor,
+             constant: torch.Tensor, pi: torch.Tensor,
+             diag_only: bool = False
+             ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Score events x [D, N] against a mixture: (label int32 [N], lse [N] =
+    ln p(x_e), pmax [N] = posterior of the assigned cluster). The label is
+    the first maximum of the posteriors estep_posteriors gives, so it is
+    the argmax of a .results row."""
+    k = means.shape[0]
+    logw = estep_logw(x, means, rinv, constant, pi, diag_only)
+    lse = estep_lse(logw)
+    w, _ = estep_posteriors(logw)
+    pmax = w.max(dim=0).values
+    idx = torch.arange(k, dtype=torch.int32).unsqueeze(1)
+    first = torch.where(w == pmax.unsqueeze(0), idx,
+                        torch.full_like(idx, k)).min(dim=0).values
+    # an event whose posteriors are all NaN matches nowhere: keep it in range
+    return first.clamp(max=k - 1), lse, pmax
 
 
 def mstep_sufficient_stats(

@@ -343,6 +343,88 @@ def estep_logw_big_f32(z: torch.Tensor, mfac32: torch.Tensor,
     return out
 
 
+def emit_factor_tables(r: torch.Tensor, rinv: torch.Tensor,
+                       means: torch.Tensor, diag_only: bool,
+                       mfac: torch.Tensor | None,
+                       mfac32: torch.Tensor | None) -> None:
+    """Emit the MFMA E-step factor tables (CUDA) from the covariance R
+    (Cholesky of R, stable for any PD covariance) into `mfac` (bf16) and
+    `mfac32`, without touching the constants: after an MDL merge, a
+    checkpoint resume or a model load the constant comes from the host path
+    and must feed the E-step unchanged.
+
+    DIAG parity through a merge: the reference's diag E-step reads
+    diag(inv(R_merged_full)) — the host merge computed the FULL-matrix
+    inverse and quirk #8 carries it into the next E-step — which is NOT
+    inv(diag(R_full)). So with diag_only the factors come from the diagonal
+    matrix with exactly that inverse; for an already-diagonal R (seed,
+    resume, every iteration after the first M-step) this is identical to R.
+    """
+    if mfac is None and mfac32 is None:
+        return
+    r_src = r
+    if diag_only:
+        d_inv = rinv.diagonal(dim1=-2, dim2=-1)
+        r_src = torch.diag_embed(1.0 / d_inv)
+    empty_b = torch.empty(0, dtype=torch.bfloat16, device=r.device)
+    empty_f = torch.empty(0, dtype=torch.float32, device=r.device)
+    hip_ext().emit_factors(
+        r_src.contiguous(), means.contiguous(),
+        mfac if mfac is not None else empty_b,
+        mfac32 if mfac32 is not None else empty_f,
+        empty_f, empty_f, empty_f,  # constants NOT recomputed (quirk #8)
+    )
+
+
+def logw_offsets(constant: torch.Tensor, pi: torch.Tensor) -> torch.Tensor:
+    """add [K] = constant + ln pi, the per-cluster offset of the factor-path
+    E-step kernels; `constant` is taken verbatim (quirk #8)."""
+    return constant + torch.log(pi)
+
+
+def model_factor_tables(means: torch.Tensor, r: torch.Tensor,
+                        rinv: torch.Tensor, constant: torch.Tensor,
+                        pi: torch.Tensor, diag_only: bool, dtype: str
+                        ) -> tuple[torch.Tensor, torch.Tensor]:
+    """(factor table, add) of a parameter set on a CUDA device, D <= 142:
+    what EmEngine._refresh_mfac and _sync_add leave in the engine's buffers.
+    The table is bf16 [K, 2, rows, cols] for dtype "bf16" and fp32
+    [K, rows, cols] for "fp32" (rows, cols from mfac_shape)."""
+    k, d = means.shape
+    shape = mfac_shape(d)
+    mfac = torch.empty(k, *shape, dtype=torch.bfloat16, device=means.device)
+    mfac32 = (torch.empty(k, *shape[1:], dtype=torch.float32,
+                          device=means.device)
+              if dtype == "fp32" else None)
+    emit_factor_tables(r, rinv, means, diag_only, mfac, mfac32)
+    return (mfac32 if mfac32 is not None else mfac,
+            logw_offsets(constant, pi))
+
+
+def estep_classify_available(device: torch.device, d: int) -> bool:
+    """Classify kernel gate: D <= 31, any K."""
+    return device.type == "cuda" and 1 <= d <= 31
+
+
+def estep_classify(x_event_major: torch.Tensor, center: torch.Tensor,
+                   fac: torch.Tensor, add: torch.Tensor, dtype: str
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Score events against a mixture (CUDA, D <= 31): x fp32 [N, D] in the
+    file's own event-major layout, center [D], the factor table and add of
+    model_factor_tables. Returns (label int32 [N] = first argmax of the
+    log-weights, lse fp32 [N] = ln p(x), pmax fp32 [N] = posterior of the
+    assigned cluster). One kernel; no [K, N] array is written."""
+    n = x_event_major.shape[0]
+    dev = x_event_major.device
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    lse = torch.empty(n, dtype=torch.float32, device=dev)
+    pmax = torch.empty(n, dtype=torch.float32, device=dev)
+    entry = (hip_ext().estep_classify_f32 if dtype == "fp32"
+             else hip_ext().estep_classify)
+    entry(x_event_major, center, fac, add, label, lse, pmax)
+    return label, lse, pmax
+
+
 def split_bf16_planes(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Persistent hi/lo bf16 split of fp32 data (x = hi + lo + O(2^-18 x))."""
     hi = x.to(torch.bfloat16)

@@ -533,6 +533,68 @@ void estep_fused_lds2(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
   HIP_CHECK(hipGetLastError());
 }
 
+// The classify entry points: x event-major fp32 [N,D], center [D], the
+// factor table in the precision of Fac, add [K]; label int32 [N], lse and
+// pmax fp32 [N]. One block per 256 events, nothing else written.
+template <typename Fac, typename Kernel>
+void launch_classify(const char* name, Kernel kernel, const torch::Tensor& x,
+                     const torch::Tensor& center, const torch::Tensor& fac,
+                     const torch::Tensor& add, torch::Tensor& label,
+                     torch::Tensor& lse, torch::Tensor& pmax) {
+  using In = typename Fac::In;
+  constexpr bool f32 = std::is_same<In, float>::value;
+  const auto dt = f32 ? torch::kFloat32 : torch::kBFloat16;
+  const char* dtn = f32 ? "fp32" : "bf16";
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                  x.scalar_type() == torch::kFloat32 && x.dim() == 2,
+              name, ": x must be contiguous fp32 [N,D] on device");
+  TORCH_CHECK(fac.is_cuda() && fac.is_contiguous() && fac.scalar_type() == dt,
+              name, ": factor table must be contiguous ", dtn, " on device");
+  check_f32(center, "center");
+  check_f32(add, "add");
+  check_f32(lse, "lse");
+  check_f32(pmax, "pmax");
+  TORCH_CHECK(label.is_cuda() && label.is_contiguous() &&
+                  label.scalar_type() == torch::kInt32,
+              name, ": label must be contiguous int32 on device");
+  const int64_t n = x.size(0);
+  const int64_t d64 = x.size(1);
+  const int64_t k64 = add.numel();
+  TORCH_CHECK(d64 >= 1 && d64 <= 31, name, " needs 1 <= D <= 31");
+  TORCH_CHECK(k64 >= 1 && k64 <= INT32_MAX && n >= 1, name,
+              " needs K >= 1 and N >= 1");
+  TORCH_CHECK(center.numel() == d64, name, ": center must be [D]");
+  TORCH_CHECK(fac.numel() >= k64 * Fac::CELLS, name,
+              ": factor table too small");
+  TORCH_CHECK(label.numel() == n && lse.numel() == n && pmax.numel() == n,
+              name, ": label, lse and pmax must be [N]");
+  const int64_t nblk = (n + gmm::EST_BE - 1) / gmm::EST_BE;
+  TORCH_CHECK(nblk <= INT32_MAX, name, ": N too large for one launch");
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)nblk), dim3(kNT),
+                     gmm::cls_lds_bytes<Fac>(), stream(),
+                     x.data_ptr<float>(), center.data_ptr<float>(),
+                     data_as<In>(fac), add.data_ptr<float>(),
+                     label.data_ptr<int>(), lse.data_ptr<float>(),
+                     pmax.data_ptr<float>(), (int)d64, (int)k64, n);
+  HIP_CHECK(hipGetLastError());
+}
+
+void estep_classify(torch::Tensor x, torch::Tensor center, torch::Tensor mfac,
+                    torch::Tensor add, torch::Tensor label, torch::Tensor lse,
+                    torch::Tensor pmax) {
+  launch_classify<gmm::FacB16>("estep_classify", gmm::estep_classify_kernel,
+                               x, center, mfac, add, label, lse, pmax);
+}
+
+void estep_classify_f32(torch::Tensor x, torch::Tensor center,
+                        torch::Tensor mfac32, torch::Tensor add,
+                        torch::Tensor label, torch::Tensor lse,
+                        torch::Tensor pmax) {
+  launch_classify<gmm::FacF32>("estep_classify_f32",
+                               gmm::estep_classify_f32_kernel, x, center,
+                               mfac32, add, label, lse, pmax);
+}
+
 void estep_logw_big(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
                     torch::Tensor logw) {
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
@@ -872,6 +934,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "small-K exact-f32 fused E-step (v1)");
   m.def("estep_fused", &estep_fused,
         "fused bf16-MFMA E-step: posteriors + likelihood partials");
+  m.def("estep_classify", &estep_classify,
+        "bf16-MFMA classify (D <= 31): label / lse / pmax per event");
+  m.def("estep_classify_f32", &estep_classify_f32,
+        "exact-f32 MFMA classify (D <= 31): label / lse / pmax per event");
   m.def("mfma_probe", &mfma_probe, "bf16 MFMA fragment-layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 bf16 layout probe");
 }

@@ -1594,6 +1594,8 @@ exp_sub_lse_kernel(const float* __restrict__ logw,
 
 // the five MFMA fused E-step kernels for D <= 31
 #include "estep_fused.hip"
+// the classify kernels (score new events): label / lse / pmax per event
+#include "estep_classify.hip"
 
 namespace gmm {
 

@@ -141,6 +141,49 @@ def write_summary(path: str, state, enable_output: bool = True) -> None:
                 f.write("\n\n")
 
 
+def read_summary(path: str) -> dict[str, np.ndarray]:
+    """Parses a .summary file in the layout format_cluster_block writes
+    (this project's or the reference's): pi [K], N [K], means [K, D] and
+    R [K, D, D] as float32. The file holds %.3f / %f text, so the values
+    are rounded to that. Raises ValueError on anything else."""
+    with open(path, "r") as f:
+        lines = [ln.strip() for ln in f]
+    pi, n, means, rs = [], [], [], []
+    i = 0
+    try:
+        while i < len(lines):
+            if not lines[i].startswith("Cluster #"):
+                if lines[i]:
+                    raise ValueError(f"unexpected line {i + 1}: {lines[i]!r}")
+                i += 1
+                continue
+            pi.append(float(lines[i + 1].split("Probability:")[1]))
+            n.append(float(lines[i + 2].split("N:")[1]))
+            mu = [float(v) for v in lines[i + 3].split("Means:")[1].split()]
+            d = len(mu)
+            if d == 0 or lines[i + 5] != "R Matrix:":
+                raise ValueError(f"malformed cluster block at line {i + 1}")
+            rows = [[float(v) for v in lines[i + 6 + j].split()]
+                    for j in range(d)]
+            if any(len(row) != d for row in rows):
+                raise ValueError(f"R matrix at line {i + 6} is not {d}x{d}")
+            means.append(mu)
+            rs.append(rows)
+            i += 6 + d
+    except IndexError:
+        raise ValueError(f"truncated summary file: {path}") from None
+    if not pi:
+        raise ValueError(f"no cluster blocks in {path}")
+    if any(len(mu) != len(means[0]) for mu in means):
+        raise ValueError(f"clusters of different dimension in {path}")
+    return {
+        "pi": np.asarray(pi, dtype=np.float32),
+        "N": np.asarray(n, dtype=np.float32),
+        "means": np.asarray(means, dtype=np.float32),
+        "R": np.asarray(rs, dtype=np.float32),
+    }
+
+
 def write_results(path: str, data_by_event: np.ndarray,
                   memberships: np.ndarray,
                   chunk: int = 65536) -> None:
