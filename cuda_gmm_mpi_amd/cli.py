@@ -72,6 +72,11 @@ def make_parser() -> argparse.ArgumentParser:
                    help="save the fitted model as a .npz that "
                         "`python -m cuda_gmm_mpi_amd.classify` scores new "
                         "data with")
+    p.add_argument("--weights", default=None, metavar="FILE",
+                   help="per-event training weights: a one-column .bin or "
+                        "CSV file with one weight >= 0 per event (0 leaves "
+                        "the event out of the fit; it still gets its row in "
+                        ".results). The summary's N are weighted counts")
     p.add_argument("--gpus", type=int, default=None,
                    help="spawn N single-GPU worker processes on this node "
                         "(one rank per GPU over RCCL)")
@@ -112,12 +117,15 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                    profile_report: bool = False,
                    scatter_input: bool = False,
                    striped_results: bool = False,
-                   save_model: str | None = None) -> dict:
+                   save_model: str | None = None,
+                   weights: np.ndarray | None = None) -> dict:
     """Full pipeline on already-initialized process group. Returns a result
     dict (rank 0) with num_clusters / rissanen / likelihood.
 
     With scatter_input, only rank 0 passes data (others None): shards are
     scattered and seeding stats broadcast (parallel.dist.distribute_input).
+    ``weights`` [N] are per-event training weights (engine.build_engine);
+    they are not scattered, so the two do not combine.
     """
     rank, local_rank, world = pdist.rank(), 0, pdist.world_size()
     if device == "cuda":
@@ -134,9 +142,10 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
             full, cfg.num_clusters)
         engine = build_engine_sharded(shard, cfg, n_tot, mean, var,
                                       seed_means, device=device,
-                                      profile=prof)
+                                      profile=prof, weights=weights)
     else:
-        engine = build_engine(data, cfg, device=device, profile=prof)
+        engine = build_engine(data, cfg, device=device, profile=prof,
+                              weights=weights)
     if profile_report:
         # graph replay bypasses the per-bucket hipEvent timers
         engine.use_graphs = False
@@ -164,7 +173,7 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
         # rank order, each ends with a newline, so
         # `cat out.results.0 out.results.1 ...` == the gathered file.
         if cfg.enable_output and write_results:
-            s0, e0 = pdist.shard_bounds(engine.n_total, world, rank)
+            s0, e0 = pdist.shard_bounds(engine.n_events_total, world, rank)
             local = (shard.numpy() if shard is not None
                      else np.asarray(data[s0:e0], dtype=np.float32))
             gio.write_results(f"{outfile}.results.{rank}", local,
@@ -196,7 +205,8 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
         "total_em_iterations": engine.total_em_iterations,
         "em_iterations_per_sec": (engine.total_em_iterations / elapsed
                                   if elapsed > 0 else 0.0),
-        "n_events": engine.n_total,
+        "n_events": engine.n_events_total,
+        "weight_total": float(engine.n_total),
     }
 
 
@@ -228,6 +238,10 @@ def main(argv=None) -> int:
         cfg = config_from_args(args)
     except ValueError as e:
         print(str(e))
+        return 1
+    if args.weights and args.scatter_input:
+        print("--weights cannot be combined with --scatter-input "
+              "(weights are not scattered)\n")
         return 1
 
     device = args.device
@@ -284,11 +298,25 @@ def main(argv=None) -> int:
             bad = int((~np.isfinite(data)).sum())
             print(f"WARNING: input contains {bad} non-finite values; "
                   "results will be degenerate", file=sys.stderr)
+        weights = None
+        if args.weights:
+            # every rank reads the file (like the data on this path); a
+            # bad file is a usage error on all of them alike
+            from .engine import validate_weights
+            try:
+                wdata = gio.read_data(args.weights)
+                if wdata.ndim != 2 or wdata.shape[1] != 1:
+                    raise ValueError(
+                        f"expected one column, got shape {wdata.shape}")
+                weights = validate_weights(wdata, data.shape[0]).numpy()
+            except (OSError, ValueError) as e:
+                print(f"Invalid weights file. ({e})\n")
+                return 1
         result = run_clustering(
             data, cfg, args.outfile, device,
             write_results=args.write_results, profile_report=args.profile,
             scatter_input=scatter, striped_results=args.striped_results,
-            save_model=args.save_model,
+            save_model=args.save_model, weights=weights,
         )
         if rank == 0 and args.metrics_out:
             import json

@@ -51,16 +51,45 @@ class EmEngine:
                  num_events_total: int, center: torch.Tensor,
                  seed_means: torch.Tensor, var_per_dim: torch.Tensor,
                  device: torch.device | str = "cpu",
-                 profile: Profile | None = None):
+                 profile: Profile | None = None,
+                 weights_shard: torch.Tensor | None = None):
         self.cfg = config
         self.device = torch.device(device)
         self.rank = pdist.rank()
         self.world = pdist.world_size()
         self.n_total = num_events_total
+        # rows in the file (all ranks): the shard geometry of the gathers.
+        # n_total is the number of OBSERVATIONS the fit stands for and
+        # differs from it only under per-event weights (below)
+        self.n_events_total = num_events_total
         self.profile = profile or Profile(self.device)
 
         shard = data_shard_by_event.to(self.device, torch.float32)
         self.n_shard = int(shard.shape[0])
+        # per-event training weights s >= 0 (None: every event counts once
+        # and nothing below is allocated or dispatched differently)
+        self.s: torch.Tensor | None = None
+        self._lns: torch.Tensor | None = None     # ln s, -inf at s == 0
+        self._lse_w: torch.Tensor | None = None   # CUDA: lse - ln s
+        self._w_s: torch.Tensor | None = None     # CPU: s * posteriors
+        if weights_shard is not None:
+            s = weights_shard.reshape(-1).to(torch.float32)
+            if int(s.numel()) != self.n_shard:
+                raise ValueError(
+                    f"weights shard has {int(s.numel())} entries for "
+                    f"{self.n_shard} events")
+            # the weight total replaces the event count everywhere the fit
+            # counts observations (MDL score, epsilon, seed N): integer
+            # weights then behave as replicated rows. float64 over all
+            # ranks, so it is world-size independent.
+            tot = torch.tensor([float(s.double().sum()), self.n_shard],
+                               dtype=torch.float64, device=self.device)
+            pdist.all_reduce_(tot)
+            self.n_total = float(tot[0].item())
+            self.n_events_total = int(tot[1].item())
+            num_events_total = int(self.n_total)
+            self.s = s.to(self.device).contiguous()
+            self._lns = torch.log(self.s)
         self.d = int(shard.shape[1])
         self.center = center.to(self.device, torch.float32)       # [D]
         shard = shard - self.center.unsqueeze(0)
@@ -93,6 +122,11 @@ class EmEngine:
         self.use_lds_estep = F.estep_fused_lds_available(
             self.device, config.estep_dtype, self.d, k0,
         )
+        if self.s is not None:
+            # the weights ride on the lse the M-step kernels subtract; the
+            # LDS variant writes posteriors and has no lse. The lse family
+            # handles any K.
+            self.use_lds_estep = False
         self.use_big_estep = F.estep_big_available(
             self.device, config.estep_dtype, self.d,
         ) and not self.use_fused_estep
@@ -139,7 +173,10 @@ class EmEngine:
             torch.empty(self.n_shard, dtype=torch.float32, device=self.device)
             if self.device.type == "cuda" else None
         )
-        self.epsilon = em_epsilon(self.d, num_events_total)
+        if self.s is not None and self.device.type == "cuda":
+            # a separate buffer: _lse stays the normalizer of posteriors()
+            self._lse_w = torch.empty_like(self._lse)
+        self.epsilon = em_epsilon(self.d, self.n_total)
         self.likelihood = 0.0
         # hipGraph capture of the EM iteration (launch-overhead elimination);
         # per-K graphs, lazily captured. Disable with use_graphs=False or
@@ -233,6 +270,11 @@ class EmEngine:
         only reads the likelihood after its FINAL iteration — the
         reference computes-and-discards it every iteration)."""
         st = self.state.shrink(k)
+        weighted = self.s is not None
+        want_lik = need_lik
+        if weighted and self.device.type == "cuda":
+            # the event-weight kernel below produces the likelihood
+            need_lik = False
         with self.profile.time("e_step"):
             self._w_is_logw = False
             if self.use_fused_estep and self.use_lds_estep:
@@ -284,7 +326,20 @@ class EmEngine:
                     self.x_estep, st.means, st.Rinv, st.constant, st.pi,
                     self.cfg.diag_only, out=self.w[:k],
                 )
-                w, lik = F.estep_posteriors(logw)
+                if weighted:
+                    # w stays normalized; the M-step reads s * w
+                    w, self._w_s, lik = F.estep_posteriors_weighted(
+                        logw, self.s)
+                else:
+                    w, lik = F.estep_posteriors(logw)
+            if weighted and self.device.type == "cuda":
+                if not self._w_is_logw:
+                    raise RuntimeError(
+                        "per-event weights need an E-step of the lse "
+                        "family (use_lds_estep must stay off)")
+                lik = F.event_weight_lse(self._lse, self.s, self._lns,
+                                         self._lse_w, want_lik,
+                                         lik_out=self._lik_dev)
         self.profile.count("regroup")
         return lik
 
@@ -333,11 +388,15 @@ class EmEngine:
         N / means / R reductions (gaussian.cu:545-686).
         """
         st = self.state.shrink(k)
+        # weighted fits: the staged weight is s * posterior — on CUDA the
+        # same kernels read the shifted lse, on CPU the product itself
+        w = self.w[:k] if self._w_s is None else self._w_s
+        lse = self._lse if self._lse_w is None else self._lse_w
         with self.profile.time("m_step"):
             packed = F.mstep_moments(
-                self.x, self.w[:k], precision=self.cfg.mstep_precision,
+                self.x, w, precision=self.cfg.mstep_precision,
                 x_split=self.x_split,
-                lse=self._lse if getattr(self, "_w_is_logw", False) else None)
+                lse=lse if getattr(self, "_w_is_logw", False) else None)
         with self.profile.time("comm"):
             pdist.all_reduce_(packed)
         lazy = (self._lazy_rinv and self._add is not None
@@ -742,11 +801,11 @@ class EmEngine:
         if self.rank != 0:
             torch.distributed.send(w_shard.contiguous(), dst=0)
             return None
-        out = np.empty((k, self.n_total), dtype=np.float32)
-        s0, e0 = pdist.shard_bounds(self.n_total, self.world, 0)
+        out = np.empty((k, self.n_events_total), dtype=np.float32)
+        s0, e0 = pdist.shard_bounds(self.n_events_total, self.world, 0)
         out[:, s0:e0] = w_shard.cpu().numpy()
         for r in range(1, self.world):
-            s, e = pdist.shard_bounds(self.n_total, self.world, r)
+            s, e = pdist.shard_bounds(self.n_events_total, self.world, r)
             buf = torch.empty(k, e - s, dtype=torch.float32,
                               device=w_shard.device)
             torch.distributed.recv(buf, src=r)
@@ -756,13 +815,21 @@ class EmEngine:
 
 def build_engine(data_by_event: np.ndarray | torch.Tensor, config: GmmConfig,
                  device: torch.device | str = "cpu",
-                 profile: Profile | None = None) -> EmEngine:
+                 profile: Profile | None = None,
+                 weights: np.ndarray | torch.Tensor | None = None
+                 ) -> EmEngine:
     """Build an engine from rank-consistent full data.
 
     Every rank passes the same full dataset (CLI: rank 0 broadcasts it
     first — see cli.run_clustering); each rank keeps only its shard.
     Seeding statistics (strided means, per-dim variance, global center)
     are computed from the full data so results are world-size independent.
+
+    ``weights`` [N] (or [N, 1]) gives every event a weight s >= 0: the fit
+    treats event e as s_e observations (0 leaves it out). Centre and
+    variance become the weighted ones and the strided seeds are drawn from
+    the events with s > 0 in file order, so a 0/1 mask fits exactly like
+    the subset and integer weights like replicated rows.
     """
     if isinstance(data_by_event, np.ndarray):
         data = torch.from_numpy(np.ascontiguousarray(data_by_event, np.float32))
@@ -771,28 +838,72 @@ def build_engine(data_by_event: np.ndarray | torch.Tensor, config: GmmConfig,
     n, d = data.shape
     config.validate()
 
-    mean = data.double().mean(dim=0)
-    var = data.double().pow(2).mean(dim=0) - mean * mean
-    center = mean.float() if config.center_data else torch.zeros(d)
-    seed_means = seed_means_host(data, config.num_clusters)
-
     r, w = pdist.rank(), pdist.world_size()
     s, e = pdist.shard_bounds(n, w, r)
+    if weights is None:
+        mean = data.double().mean(dim=0)
+        var = data.double().pow(2).mean(dim=0) - mean * mean
+        center = mean.float() if config.center_data else torch.zeros(d)
+        seed_means = seed_means_host(data, config.num_clusters)
+        return EmEngine(
+            data[s:e], config, n, center, seed_means, var.float(),
+            device=device, profile=profile,
+        )
+
+    sw = validate_weights(weights, n)
+    total = sw.sum()
+    ws = sw.unsqueeze(1)
+    mean = (data.double() * ws).sum(dim=0) / total
+    var = (data.double().pow(2) * ws).sum(dim=0) / total - mean * mean
+    center = mean.float() if config.center_data else torch.zeros(d)
+    seed_means = seed_means_host(data[sw > 0], config.num_clusters)
     return EmEngine(
         data[s:e], config, n, center, seed_means, var.float(),
-        device=device, profile=profile,
+        device=device, profile=profile, weights_shard=sw[s:e].float(),
     )
+
+
+def validate_weights(weights: np.ndarray | torch.Tensor,
+                     num_events: int) -> torch.Tensor:
+    """Per-event weights as a float64 [N] tensor; ValueError unless there is
+    one finite weight >= 0 per event and their sum is positive."""
+    sw = torch.as_tensor(np.asarray(weights)).to(torch.float64).cpu()
+    if sw.dim() == 2 and sw.shape[1] == 1:
+        sw = sw[:, 0]
+    if sw.dim() != 1 or int(sw.shape[0]) != num_events:
+        raise ValueError(
+            f"weights must be one value per event ([{num_events}] or "
+            f"[{num_events}, 1]), got shape {tuple(sw.shape)}")
+    if not bool(torch.isfinite(sw).all()):
+        raise ValueError("weights must be finite")
+    if bool((sw < 0).any()):
+        raise ValueError("weights must be >= 0")
+    # the engine holds fp32 weights: seed and centre with those very values
+    # (a weight that rounds to 0 there leaves its event out everywhere)
+    sw = sw.float().double()
+    if not bool(torch.isfinite(sw).all()):
+        raise ValueError("weights must be finite in fp32")
+    if not float(sw.sum()) > 0.0:
+        raise ValueError("weights must have a positive sum")
+    return sw
 
 
 def build_engine_sharded(shard: torch.Tensor, config: GmmConfig,
                          n_total: int, mean: torch.Tensor,
                          var: torch.Tensor, seed_means: torch.Tensor,
                          device: torch.device | str = "cpu",
-                         profile: Profile | None = None) -> EmEngine:
+                         profile: Profile | None = None,
+                         weights=None) -> EmEngine:
     """Build an engine from a pre-distributed shard (rank-0-read input:
     parallel.dist.distribute_input). `mean`/`var`/`seed_means` are the
     full-data statistics broadcast from rank 0, so results are identical
-    to the shared-filesystem `build_engine` path."""
+    to the shared-filesystem `build_engine` path. Per-event weights are not
+    scattered: passing any is an error."""
+    if weights is not None:
+        raise ValueError(
+            "per-event weights are not supported with scattered input "
+            "(--scatter-input): every rank must read the weights file; "
+            "use the shared-filesystem path (build_engine)")
     config.validate()
     d = shard.shape[1]
     center = mean.float() if config.center_data else torch.zeros(d)

@@ -63,6 +63,37 @@ def estep_lse(logw: torch.Tensor) -> torch.Tensor:
     return m + torch.log(torch.exp(logw - m.unsqueeze(0)).sum(dim=0))
 
 
+def event_weight_lse(lse: torch.Tensor, s: torch.Tensor, lns: torch.Tensor
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU twin of the event-weight kernel: (lse_w [N], weighted likelihood).
+
+    lse_w = lse - lns with +inf where s == 0 (lns = ln s, -inf there), so
+    exp(logw - lse_w) = s * posterior with an exact 0 at zero weights. The
+    likelihood is sum_e s_e lse_e over the events with s_e > 0 (0 * inf is
+    NaN, so zero-weight terms are skipped, not multiplied)."""
+    zero = s == 0
+    inf = torch.full_like(lse, float("inf"))
+    lse_w = torch.where(zero, inf, lse - lns)
+    lik = torch.where(zero, torch.zeros_like(lse), s * lse).sum()
+    return lse_w, lik
+
+
+def estep_posteriors_weighted(logw: torch.Tensor, s: torch.Tensor
+                              ) -> tuple[torch.Tensor, torch.Tensor,
+                                         torch.Tensor]:
+    """E-step of a fit with per-event weights s [N] >= 0: (w [K, N]
+    normalized posteriors, w_s [K, N] = w * s — what the M-step sums, its
+    columns sum to s — and the likelihood sum_e s_e ln p(x_e))."""
+    lse = estep_lse(logw)
+    _, lik = event_weight_lse(lse, s, torch.log(s))
+    w = torch.exp(logw - lse.unsqueeze(0))
+    # a zero-weight event contributes an exact 0 even where its posterior
+    # is NaN (lse = -inf)
+    w_s = torch.where((s == 0).unsqueeze(0), torch.zeros_like(w),
+                      w * s.unsqueeze(0))
+    return w, w_s, lik
+
+
 def classify(x: torch.Tensor, means: torch.Tensor, rinv: torch.Tensor,
              constant: torch.Tensor, pi: torch.Tensor,
              diag_only: bool = False

@@ -70,6 +70,42 @@ def estep_lse(logw: torch.Tensor, lse: torch.Tensor,
     return lik
 
 
+def event_weight_lse(lse: torch.Tensor, s: torch.Tensor, lns: torch.Tensor,
+                     lse_w: torch.Tensor, need_lik: bool = True,
+                     lik_out: torch.Tensor | None = None
+                     ) -> torch.Tensor | None:
+    """Per-event training weights on the lse family (CUDA): writes
+    lse_w [N] = lse - lns (+inf where s == 0), the shifted lse the lse-aware
+    M-step kernels read so that they stage s * posterior. ``lns`` is ln s
+    with -inf at s == 0. With ``need_lik`` returns the weighted
+    log-likelihood sum_e s_e lse_e (zero-weight events skipped), reduced
+    into ``lik_out`` [1] when one is given; fixed block partials, so it is
+    deterministic. ``lse`` is left untouched."""
+    ext = hip_ext()
+    if not need_lik:
+        ext.event_weight_lse(lse, s, lns, lse_w, lse.new_empty(0))
+        return None
+    # every launched block writes its partial slot: no zero-fill needed
+    partial = torch.empty(ext.event_weight_lse_blocks(lse.numel()),
+                          dtype=torch.float32, device=lse.device)
+    ext.event_weight_lse(lse, s, lns, lse_w, partial)
+    lik = (lik_out if lik_out is not None
+           else torch.empty(1, dtype=torch.float32, device=lse.device))
+    ext.reduce_scalar(partial, lik)
+    return lik
+
+
+def estep_posteriors_weighted(logw: torch.Tensor, s: torch.Tensor
+                              ) -> tuple[torch.Tensor, torch.Tensor,
+                                         torch.Tensor]:
+    """CPU engine path of a weighted fit: logw becomes the normalized
+    posteriors in place (like estep_posteriors); returns (w, w * s for the
+    M-step, weighted likelihood scalar tensor)."""
+    w, w_s, lik = cpu.estep_posteriors_weighted(logw, s)
+    logw.copy_(w)
+    return logw, w_s, lik
+
+
 def mstep_n_means(x_aug_t: torch.Tensor, w: torch.Tensor
                   ) -> tuple[torch.Tensor, torch.Tensor]:
     """(N [K], mean numerators [K, D]) via one rocBLAS GEMM.

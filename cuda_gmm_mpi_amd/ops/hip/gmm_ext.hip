@@ -139,6 +139,44 @@ void estep_lse(torch::Tensor logw, torch::Tensor lse,
   HIP_CHECK(hipGetLastError());
 }
 
+// Blocks event_weight_lse launches for n events: one per 4 * kNT events,
+// capped (grid-stride beyond). The likelihood partial buffer has exactly
+// this many slots, so reduce_scalar reads only slots a block has written.
+int64_t event_weight_lse_blocks(int64_t n) {
+  constexpr int64_t per_block = (int64_t)EW_VEC * kNT;
+  return std::max<int64_t>(
+      1, std::min<int64_t>((n + per_block - 1) / per_block, 2048));
+}
+
+void event_weight_lse(torch::Tensor lse, torch::Tensor s, torch::Tensor lns,
+                      torch::Tensor lse_w, torch::Tensor partial) {
+  check_f32(lse, "lse");
+  check_f32(s, "s");
+  check_f32(lns, "lns");
+  check_f32(lse_w, "lse_w");
+  check_f32(partial, "partial");
+  const int64_t n = lse.numel();
+  TORCH_CHECK(n >= 1, "empty lse");
+  TORCH_CHECK(s.numel() == n && lns.numel() == n && lse_w.numel() == n,
+              "s, lns and lse_w must be [N] like lse");
+  const int64_t grid = event_weight_lse_blocks(n);
+  // an empty partial switches the likelihood off (nothing is written)
+  TORCH_CHECK(partial.numel() == 0 || partial.numel() == grid,
+              "partial must be empty or [event_weight_lse_blocks(N)]");
+  auto aligned = [](const torch::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  const int64_t nvec = (aligned(lse) && aligned(s) && aligned(lns) &&
+                        aligned(lse_w)) ? n / EW_VEC : 0;
+  hipLaunchKernelGGL(gmm::event_weight_lse_kernel, dim3((unsigned)grid),
+                     dim3(kNT), 0, stream(), lse.data_ptr<float>(),
+                     s.data_ptr<float>(), lns.data_ptr<float>(),
+                     lse_w.data_ptr<float>(),
+                     partial.numel() ? partial.data_ptr<float>() : nullptr,
+                     nvec, n);
+  HIP_CHECK(hipGetLastError());
+}
+
 template <typename T>
 void mstep_cov_impl(const torch::Tensor& x, const torch::Tensor& w,
                     const torch::Tensor& lse, torch::Tensor& partials) {
@@ -896,6 +934,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("estep_lse", &estep_lse,
         "per-event log-sum-exp + likelihood partials (no posterior "
         "write-back; pairs with the lse-aware M-step)");
+  m.def("event_weight_lse", &event_weight_lse,
+        "lse_w = lse - ln s (+inf at s == 0) + weighted likelihood partials");
+  m.def("event_weight_lse_blocks", &event_weight_lse_blocks,
+        "block (= likelihood partial) count of event_weight_lse for N events");
   m.def("mstep_covariance_partials", &mstep_covariance_partials,
         "packed weighted second-moment partials [nchunk,K,P]");
   m.def("constants", &constants,

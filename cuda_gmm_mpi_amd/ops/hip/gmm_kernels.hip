@@ -249,6 +249,63 @@ estep_lse_kernel(const float* __restrict__ logw, float* __restrict__ lse,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Per-event training weights s_e >= 0: the lse-aware M-step kernels stage
+// exp(logw - lse), so  s_e * posterior = exp(logw - (lse - ln s_e))  and a
+// weighted M-step is the same kernels reading the shifted lse written here:
+//   lse_w[e] = lse[e] - lns[e]     (lns = ln s, -inf where s == 0)
+//   lse_w[e] = +inf where s[e] == 0, whatever lse holds (-inf - -inf is
+//              NaN): the staged weight exp(logw - inf) is then an exact 0.
+// With `partial` non-null each block also writes its share of the weighted
+// log-likelihood sum_e s_e * lse_e to partial[blockIdx.x] (zero-weight
+// terms skipped, not multiplied: 0 * inf is NaN) for reduce_scalar_kernel.
+// Every thread walks a fixed set of events in a fixed order and block_sum
+// is fixed-order: deterministic, no float atomics.
+// Memory-bound (12 B read + 4 B written per event): the first nvec * 4
+// events move as 16-byte vectors (the launcher passes nvec = 0 when a
+// pointer is not 16-byte aligned), the rest as a scalar tail.
+// ---------------------------------------------------------------------------
+#define EW_VEC 4  // events per thread and grid-stride step
+
+__device__ __forceinline__ float event_weight_one(float l, float s, float ls,
+                                                  float* acc) {
+  if (s == 0.0f) return INFINITY;
+  *acc += s * l;
+  return l - ls;
+}
+
+__global__ void __launch_bounds__(NT)
+event_weight_lse_kernel(const float* __restrict__ lse,
+                        const float* __restrict__ s,
+                        const float* __restrict__ lns,
+                        float* __restrict__ lse_w,
+                        float* __restrict__ partial, int64_t nvec,
+                        int64_t n) {
+  float acc = 0.0f;
+  const int64_t stride = (int64_t)gridDim.x * NT;
+  const int64_t t0 = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const f32x4* lse4 = reinterpret_cast<const f32x4*>(lse);
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(s);
+  const f32x4* lns4 = reinterpret_cast<const f32x4*>(lns);
+  f32x4* out4 = reinterpret_cast<f32x4*>(lse_w);
+  for (int64_t v = t0; v < nvec; v += stride) {
+    const f32x4 l = lse4[v];
+    const f32x4 sv = s4[v];
+    const f32x4 ls = lns4[v];
+    f32x4 o;
+#pragma unroll
+    for (int u = 0; u < EW_VEC; ++u)
+      o[u] = event_weight_one(l[u], sv[u], ls[u], &acc);
+    out4[v] = o;
+  }
+  for (int64_t e = nvec * EW_VEC + t0; e < n; e += stride)
+    lse_w[e] = event_weight_one(lse[e], s[e], lns[e], &acc);
+  if (partial != nullptr) {  // kernel argument: uniform over the block
+    __shared__ float wsum[NT / WAVE];
+    block_sum(acc, wsum, partial);
+  }
+}
+
 // Deterministic chunk reduction: out[j] = sum_i in[i*m + j] (fixed i
 // order). Replaces torch's generic reduce_kernel (19.6 us for the
 // [256, K*Pp] moments partials).
