@@ -77,6 +77,14 @@ def make_parser() -> argparse.ArgumentParser:
                         "CSV file with one weight >= 0 per event (0 leaves "
                         "the event out of the fit; it still gets its row in "
                         ".results). The summary's N are weighted counts")
+    p.add_argument("--seed-method", choices=["strided", "kmeans++"],
+                   default="strided",
+                   help="starting means: strided = the reference's evenly "
+                        "strided rows (depends on the file's row order); "
+                        "kmeans++ = greedy k-means++ over the full dataset")
+    p.add_argument("--seed", type=int, default=0, metavar="N",
+                   help="random seed of --seed-method kmeans++ (same seed, "
+                        "same starting means, whatever the world size)")
     p.add_argument("--gpus", type=int, default=None,
                    help="spawn N single-GPU worker processes on this node "
                         "(one rank per GPU over RCCL)")
@@ -107,6 +115,7 @@ def config_from_args(args) -> GmmConfig:
         mstep_precision=args.mstep_precision,
         checkpoint_dir=args.checkpoint_dir,
         nearest_target=args.nearest_target,
+        seed_method=args.seed_method, seed_rng=args.seed,
     )
     cfg.validate()
     return cfg
@@ -135,14 +144,19 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
     t_start = _time.perf_counter()
     shard = None
     if scatter_input:
-        from .engine import build_engine_sharded
+        from .engine import build_engine_sharded, seed_full_data
         full = (torch.from_numpy(np.ascontiguousarray(data, np.float32))
                 if rank == 0 else None)
+        cfg.validate()
+        seed_info: dict = {}
         shard, n_tot, mean, var, seed_means = pdist.distribute_input(
-            full, cfg.num_clusters)
+            full, cfg.num_clusters,
+            seed_fn=lambda d: seed_full_data(d, cfg, device),
+            seed_info=seed_info)
         engine = build_engine_sharded(shard, cfg, n_tot, mean, var,
                                       seed_means, device=device,
-                                      profile=prof, weights=weights)
+                                      profile=prof, weights=weights,
+                                      seed_indices=seed_info["indices"])
     else:
         engine = build_engine(data, cfg, device=device, profile=prof,
                               weights=weights)
@@ -207,6 +221,9 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                                   if elapsed > 0 else 0.0),
         "n_events": engine.n_events_total,
         "weight_total": float(engine.n_total),
+        "seed_method": cfg.seed_method,
+        "seed_rng": cfg.seed_rng,
+        "seed_indices": engine.seed_indices,
     }
 
 
@@ -336,6 +353,9 @@ def main(argv=None) -> int:
                     "em_iterations_per_sec":
                         result["em_iterations_per_sec"],
                     "n_events": result["n_events"],
+                    "seed_method": result["seed_method"],
+                    "seed_rng": result["seed_rng"],
+                    "seed_indices": result["seed_indices"],
                 }, f, indent=2)
         if rank == 0 and args.enable_print:
             print(f"Ideal clusters: {result['num_clusters']} "

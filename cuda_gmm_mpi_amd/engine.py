@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from .models.merge import HostClusters, reduce_order_batched
-from .models.seed import seed_means_host, seed_state
+from .models.seed import (seed_indices_strided, seed_means_host,
+                          seed_state)
 from .models.state import GmmState
 from .ops import functional as F
 from .parallel import dist as pdist
@@ -185,7 +186,9 @@ class EmEngine:
         self._graphs: dict[int, object] = {}
         self._lik_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.total_em_iterations = 0  # across the whole sweep (all Ks)
-
+        # rows of the full dataset the seed means were taken from, when the
+        # builder knows them (build_engine / build_engine_sharded set it)
+        self.seed_indices: list[int] | None = None
 
     def _refresh_mfac(self, k: int) -> None:
         """Re-emit the fused-E-step factors from the CURRENT covariance R
@@ -840,27 +843,60 @@ def build_engine(data_by_event: np.ndarray | torch.Tensor, config: GmmConfig,
 
     r, w = pdist.rank(), pdist.world_size()
     s, e = pdist.shard_bounds(n, w, r)
-    if weights is None:
+    sw = None if weights is None else validate_weights(weights, n)
+    if sw is None:
         mean = data.double().mean(dim=0)
         var = data.double().pow(2).mean(dim=0) - mean * mean
-        center = mean.float() if config.center_data else torch.zeros(d)
-        seed_means = seed_means_host(data, config.num_clusters)
-        return EmEngine(
-            data[s:e], config, n, center, seed_means, var.float(),
-            device=device, profile=profile,
-        )
-
-    sw = validate_weights(weights, n)
-    total = sw.sum()
-    ws = sw.unsqueeze(1)
-    mean = (data.double() * ws).sum(dim=0) / total
-    var = (data.double().pow(2) * ws).sum(dim=0) / total - mean * mean
+    else:
+        total = sw.sum()
+        ws = sw.unsqueeze(1)
+        mean = (data.double() * ws).sum(dim=0) / total
+        var = (data.double().pow(2) * ws).sum(dim=0) / total - mean * mean
     center = mean.float() if config.center_data else torch.zeros(d)
-    seed_means = seed_means_host(data[sw > 0], config.num_clusters)
-    return EmEngine(
+    if config.seed_method == "strided" or w == 1:
+        seed_means, seed_idx = seed_full_data(data, config, device, sw)
+    else:
+        # data-dependent seeding runs once, on rank 0, and is broadcast: the
+        # seeds are then the same whatever the world size
+        k = config.num_clusters
+        if r == 0:
+            seed_means, seed_idx = seed_full_data(data, config, device, sw)
+        else:
+            seed_means = torch.zeros(k, d, dtype=torch.float32)
+            seed_idx = torch.zeros(k, dtype=torch.long)
+        pdist.broadcast_(seed_means)
+        pdist.broadcast_(seed_idx)
+    engine = EmEngine(
         data[s:e], config, n, center, seed_means, var.float(),
-        device=device, profile=profile, weights_shard=sw[s:e].float(),
+        device=device, profile=profile,
+        weights_shard=None if sw is None else sw[s:e].float(),
     )
+    engine.seed_indices = [int(i) for i in seed_idx]
+    return engine
+
+
+def seed_full_data(data: torch.Tensor, config: GmmConfig,
+                   device: torch.device | str = "cpu",
+                   weights: torch.Tensor | None = None
+                   ) -> tuple[torch.Tensor, torch.Tensor]:
+    """(seed means fp32 [K, D], their rows int64 [K]) of the full host
+    dataset [N, D] under ``config.seed_method``; ``weights`` [N] as
+    validate_weights returns them. The strided rows are those of the events
+    with weight > 0 in file order; k-means++ (functional.seed_kmeanspp, on
+    ``device``) weighs every event by s and never picks one with s == 0."""
+    k = config.num_clusters
+    if config.seed_method == "kmeans++":
+        means, idx, _ = F.seed_kmeanspp(
+            data, k, config.seed_rng,
+            weights=None if weights is None else weights.float(),
+            device=device)
+        return means, idx
+    if weights is None:
+        return (seed_means_host(data, k),
+                seed_indices_strided(int(data.shape[0]), k))
+    live = torch.nonzero(weights > 0).reshape(-1)
+    return (seed_means_host(data[weights > 0], k),
+            live[seed_indices_strided(int(live.numel()), k)])
 
 
 def validate_weights(weights: np.ndarray | torch.Tensor,
@@ -893,7 +929,7 @@ def build_engine_sharded(shard: torch.Tensor, config: GmmConfig,
                          var: torch.Tensor, seed_means: torch.Tensor,
                          device: torch.device | str = "cpu",
                          profile: Profile | None = None,
-                         weights=None) -> EmEngine:
+                         weights=None, seed_indices=None) -> EmEngine:
     """Build an engine from a pre-distributed shard (rank-0-read input:
     parallel.dist.distribute_input). `mean`/`var`/`seed_means` are the
     full-data statistics broadcast from rank 0, so results are identical
@@ -907,7 +943,10 @@ def build_engine_sharded(shard: torch.Tensor, config: GmmConfig,
     config.validate()
     d = shard.shape[1]
     center = mean.float() if config.center_data else torch.zeros(d)
-    return EmEngine(
+    engine = EmEngine(
         shard.to(torch.float32), config, n_total, center, seed_means,
         var.float(), device=device, profile=profile,
     )
+    if seed_indices is not None:
+        engine.seed_indices = [int(i) for i in seed_indices]
+    return engine

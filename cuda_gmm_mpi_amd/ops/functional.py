@@ -14,6 +14,7 @@ import os
 
 import torch
 
+from ..models import seed as seed_mod
 from . import cpu_reference as cpu
 from .backend import hip_ext
 
@@ -459,6 +460,92 @@ def estep_classify(x_event_major: torch.Tensor, center: torch.Tensor,
              else hip_ext().estep_classify)
     entry(x_event_major, center, fac, add, label, lse, pmax)
     return label, lse, pmax
+
+
+# stages of a seeding round (bits of seed_kmeanspp_rounds' `stages`)
+SEED_SAMPLE, SEED_EVALUATE, SEED_CHOOSE, SEED_COMMIT = 1, 2, 4, 8
+SEED_ALL = SEED_SAMPLE | SEED_EVALUATE | SEED_CHOOSE | SEED_COMMIT
+
+
+def seed_kmeanspp_workspace(x_event_major: torch.Tensor, k: int,
+                            seed_rng: int,
+                            weights: torch.Tensor | None = None) -> dict:
+    """Device buffers of one k-means++ seeding of x (CUDA fp32 [N, D],
+    event-major): the uniforms (drawn on the host, uploaded once), the work
+    buffers and the per-round record, keyed by the argument names of the
+    extension's seed_kmeanspp_rounds. Nothing is launched."""
+    ext = hip_ext()
+    dev = x_event_major.device
+    n = int(x_event_major.shape[0])
+    nl = seed_mod.kmeanspp_num_candidates(k)
+    nblk = int(ext.seed_kmeanspp_blocks(n))
+    f32 = dict(dtype=torch.float32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    return {
+        "x": x_event_major,
+        "s": (weights.to(dev, torch.float32).reshape(-1).contiguous()
+              if weights is not None else torch.empty(0, **f32)),
+        "u": torch.from_numpy(seed_mod.kmeanspp_uniforms(k, seed_rng)).to(dev),
+        "m": torch.empty(n, **f32),
+        "scratch": torch.empty((nl, n), **f32),
+        "pot_part": torch.empty((nblk, 8), **f64),
+        "sm_part": torch.empty(nblk, **f64),
+        "s_part": torch.empty(nblk, **f64),
+        "cand": torch.zeros((k, 8), dtype=torch.int64, device=dev),
+        "winner": torch.zeros(k, dtype=torch.int32, device=dev),
+        "index": torch.zeros(k, dtype=torch.int64, device=dev),
+        "pots": torch.zeros((k, 8), **f64),
+    }
+
+
+def seed_kmeanspp_rounds(ws: dict, t0: int, t1: int,
+                         stages: int = SEED_ALL) -> None:
+    """Enqueue the selected stages of seeding rounds [t0, t1) on the buffers
+    of seed_kmeanspp_workspace; no host synchronisation."""
+    hip_ext().seed_kmeanspp_rounds(
+        ws["x"], ws["s"], ws["u"], ws["m"], ws["scratch"], ws["pot_part"],
+        ws["sm_part"], ws["s_part"], ws["cand"], ws["winner"], ws["index"],
+        ws["pots"], int(t0), int(t1), int(stages))
+
+
+def seed_kmeanspp_trace(ws: dict) -> dict:
+    """The per-round record of a finished seeding in the layout of
+    models.seed.seed_means_kmeanspp's trace (host tensors)."""
+    k = int(ws["u"].shape[0])
+    nl = int(ws["scratch"].shape[0])
+    cands = ws["cand"][:, :nl].cpu()
+    pots = ws["pots"][:, :nl].cpu()
+    if nl > 1:  # round 0 has a single candidate
+        cands[0, 1:] = -1
+        pots[0, 1:] = float("nan")
+    return {"candidates": cands, "winner": ws["winner"].cpu().long(),
+            "potentials": pots}
+
+
+def seed_kmeanspp(data, k: int, seed_rng: int, weights=None,
+                  device: torch.device | str = "cpu"
+                  ) -> tuple[torch.Tensor, torch.Tensor, dict]:
+    """Greedy k-means++ seeds of the full dataset ``data`` [N, D] (contract:
+    models.seed.seed_means_kmeanspp). Returns host tensors (means fp32
+    [K, D], indices int64 [K], trace).
+
+    CPU: the float64 host implementation. CUDA: the data is uploaded once to
+    ``device``, the gfx950 kernels run all K rounds without a host
+    synchronisation, and the indices and the trace come back in one copy at
+    the end; the upload is freed on return. The GPU draws from fp32
+    distances, so a draw that lands within rounding of an interval boundary
+    may differ from the CPU's; either is a valid k-means++ seeding."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return seed_mod.seed_means_kmeanspp(data, k, seed_rng, weights)
+    hip_ext()  # loud failure when unbuilt: no eager fallback
+    host = torch.as_tensor(data).to(torch.float32).contiguous()
+    w = None if weights is None else torch.as_tensor(weights)
+    ws = seed_kmeanspp_workspace(host.to(device), k, seed_rng, w)
+    seed_kmeanspp_rounds(ws, 0, k)
+    idx = ws["index"].cpu()
+    trace = seed_kmeanspp_trace(ws)
+    return host[idx], idx, trace
 
 
 def split_bf16_planes(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:

@@ -633,6 +633,114 @@ void estep_classify_f32(torch::Tensor x, torch::Tensor center,
                                mfac32, add, label, lse, pmax);
 }
 
+// Greedy k-means++ seeding (seed_kmeanspp.hip). One block per 256 events;
+// the block-partial buffers have exactly this many rows.
+int64_t seed_kmeanspp_blocks(int64_t n) {
+  return (n + gmm::SEED_BE - 1) / gmm::SEED_BE;
+}
+
+// Stages of a round, as bits of `stages`.
+constexpr int64_t kSeedSample = 1, kSeedEvaluate = 2, kSeedChoose = 4,
+                  kSeedCommit = 8;
+
+// Enqueue the selected stages of rounds [t0, t1) on the current stream; no
+// synchronisation, nothing is read back. x fp32 [N,D] event-major, s fp32 [N]
+// or empty (unweighted), u float64 [K,8] uniforms. Work buffers: m fp32 [N],
+// scratch fp32 [L,N], pot_part float64 [blocks,8], sm_part / s_part float64
+// [blocks]. Per-round record: cand int64 [K,8] (round t draws into row t, or
+// the caller fills it when the sample stage is left out), winner int32 [K],
+// index int64 [K], pots float64 [K,8]. Round 0 has one candidate; rounds
+// >= 1 have L. With all stages, rounds [0, K) are the whole seeding.
+void seed_kmeanspp_rounds(torch::Tensor x, torch::Tensor s, torch::Tensor u,
+                          torch::Tensor m, torch::Tensor scratch,
+                          torch::Tensor pot_part, torch::Tensor sm_part,
+                          torch::Tensor s_part, torch::Tensor cand,
+                          torch::Tensor winner, torch::Tensor index,
+                          torch::Tensor pots, int64_t t0, int64_t t1,
+                          int64_t stages) {
+  auto check = [](const torch::Tensor& t, torch::ScalarType dt,
+                  const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == dt,
+                "seed_kmeanspp: ", name,
+                " must be contiguous on device with the documented dtype");
+  };
+  check(x, torch::kFloat32, "x");
+  check(u, torch::kFloat64, "u");
+  check(m, torch::kFloat32, "m");
+  check(scratch, torch::kFloat32, "scratch");
+  check(pot_part, torch::kFloat64, "pot_part");
+  check(sm_part, torch::kFloat64, "sm_part");
+  check(s_part, torch::kFloat64, "s_part");
+  check(cand, torch::kInt64, "cand");
+  check(winner, torch::kInt32, "winner");
+  check(index, torch::kInt64, "index");
+  check(pots, torch::kFloat64, "pots");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 &&
+                  x.size(1) <= INT32_MAX,
+              "seed_kmeanspp: x must be [N,D] with N, D >= 1");
+  const int64_t n = x.size(0);
+  const int d = (int)x.size(1);
+  const int64_t nblk = seed_kmeanspp_blocks(n);
+  TORCH_CHECK(nblk <= INT32_MAX, "seed_kmeanspp: N too large for one launch");
+  const float* sp = nullptr;
+  if (s.numel() != 0) {
+    check(s, torch::kFloat32, "s");
+    TORCH_CHECK(s.numel() == n, "seed_kmeanspp: s must be [N]");
+    sp = s.data_ptr<float>();
+  }
+  TORCH_CHECK(scratch.dim() == 2 && scratch.size(1) == n &&
+                  scratch.size(0) >= 1 && scratch.size(0) <= gmm::SEED_LMAX,
+              "seed_kmeanspp: scratch must be [L,N] with 1 <= L <= 8");
+  const int nl = (int)scratch.size(0);
+  const int64_t k = u.dim() == 2 ? u.size(0) : 0;
+  TORCH_CHECK(k >= 1 && u.size(1) == gmm::SEED_LMAX,
+              "seed_kmeanspp: u must be [K,8]");
+  TORCH_CHECK(m.numel() == n, "seed_kmeanspp: m must be [N]");
+  TORCH_CHECK(pot_part.numel() == nblk * gmm::SEED_LMAX &&
+                  sm_part.numel() == nblk && s_part.numel() == nblk,
+              "seed_kmeanspp: partial buffers must have "
+              "seed_kmeanspp_blocks(N) rows");
+  TORCH_CHECK(cand.numel() == k * gmm::SEED_LMAX &&
+                  pots.numel() == k * gmm::SEED_LMAX && winner.numel() == k &&
+                  index.numel() == k,
+              "seed_kmeanspp: cand/pots must be [K,8], winner/index [K]");
+  TORCH_CHECK(0 <= t0 && t0 <= t1 && t1 <= k,
+              "seed_kmeanspp: rounds must satisfy 0 <= t0 <= t1 <= K");
+  auto st = stream();
+  const dim3 grid((uint32_t)nblk), one(1), nt(kNT);
+  const int x_vec = reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+  if (t0 == 0 && t0 < t1 && (stages & kSeedSample))
+    hipLaunchKernelGGL(gmm::seed_weight_partials_kernel, grid, nt, 0, st, sp,
+                       s_part.data_ptr<double>(), n);
+  for (int64_t t = t0; t < t1; ++t) {
+    const int nlt = t == 0 ? 1 : nl;
+    int64_t* cand_t = cand.data_ptr<int64_t>() + t * gmm::SEED_LMAX;
+    if (stages & kSeedSample)
+      hipLaunchKernelGGL(gmm::seed_sample_kernel, one, nt, 0, st, sp,
+                         m.data_ptr<float>(), sm_part.data_ptr<double>(),
+                         s_part.data_ptr<double>(),
+                         u.data_ptr<double>() + t * gmm::SEED_LMAX, nlt,
+                         (int)(t == 0), cand_t, nblk, n);
+    if (stages & kSeedEvaluate)
+      hipLaunchKernelGGL(gmm::seed_evaluate_kernel, grid, nt, 0, st,
+                         x.data_ptr<float>(), sp, m.data_ptr<float>(), cand_t,
+                         nlt, (int)(t == 0), scratch.data_ptr<float>(),
+                         pot_part.data_ptr<double>(), x_vec, d, n);
+    if (stages & kSeedChoose)
+      hipLaunchKernelGGL(gmm::seed_choose_kernel, one, nt, 0, st,
+                         pot_part.data_ptr<double>(), cand_t, nlt,
+                         winner.data_ptr<int>() + t,
+                         index.data_ptr<int64_t>() + t,
+                         pots.data_ptr<double>() + t * gmm::SEED_LMAX, nblk);
+    if (stages & kSeedCommit)
+      hipLaunchKernelGGL(gmm::seed_commit_kernel, grid, nt, 0, st,
+                         scratch.data_ptr<float>(),
+                         winner.data_ptr<int>() + t, nlt, sp,
+                         m.data_ptr<float>(), sm_part.data_ptr<double>(), n);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 void estep_logw_big(torch::Tensor z, torch::Tensor mfac, torch::Tensor add,
                     torch::Tensor logw) {
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
@@ -980,6 +1088,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16-MFMA classify (D <= 31): label / lse / pmax per event");
   m.def("estep_classify_f32", &estep_classify_f32,
         "exact-f32 MFMA classify (D <= 31): label / lse / pmax per event");
+  m.def("seed_kmeanspp_rounds", &seed_kmeanspp_rounds,
+        "greedy k-means++ seeding: enqueue stages (1 sample | 2 evaluate | "
+        "4 choose | 8 commit) of rounds [t0, t1)");
+  m.def("seed_kmeanspp_blocks", &seed_kmeanspp_blocks,
+        "block (= partial row) count of the seeding kernels for N events");
   m.def("mfma_probe", &mfma_probe, "bf16 MFMA fragment-layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 bf16 layout probe");
 }

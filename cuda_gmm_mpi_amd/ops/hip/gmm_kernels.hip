@@ -1653,6 +1653,8 @@ exp_sub_lse_kernel(const float* __restrict__ logw,
 #include "estep_fused.hip"
 // the classify kernels (score new events): label / lse / pmax per event
 #include "estep_classify.hip"
+// greedy k-means++ seeding: sample / evaluate / choose / commit per round
+#include "seed_kmeanspp.hip"
 
 namespace gmm {
 

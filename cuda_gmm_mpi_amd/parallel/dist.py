@@ -114,7 +114,8 @@ def destroy() -> None:
         dist.destroy_process_group()
 
 
-def distribute_input(data: torch.Tensor | None, num_clusters: int):
+def distribute_input(data: torch.Tensor | None, num_clusters: int,
+                     seed_fn=None, seed_info: dict | None = None):
     """Rank-0-read input distribution (reference: MPI_Bcast of the whole
     dataset, gaussian.cu:193-200 — here each rank receives only its SHARD
     via point-to-point sends, sized for N >> full-replication).
@@ -124,8 +125,18 @@ def distribute_input(data: torch.Tensor | None, num_clusters: int):
     shard plus the global seeding statistics, computed on rank 0 from the
     full data with exactly the same code as the shared-filesystem path
     (engine.build_engine) so both paths produce identical results.
+
+    ``seed_fn(data) -> (means [K, D], rows [K])`` replaces the strided seeds
+    (engine.seed_full_data under the run's config: the data-dependent
+    seeding); rank 0 calls it on the full data before the stats broadcast.
+    A ``seed_info`` dict receives the broadcast rows under "indices".
     """
-    from ..models.seed import seed_means_host
+    from ..models.seed import seed_indices_strided
+
+    if seed_fn is None:
+        def seed_fn(full):
+            idx = seed_indices_strided(int(full.shape[0]), num_clusters)
+            return full[idx].to(torch.float32), idx
 
     w, r = world_size(), rank()
     if w == 1:
@@ -133,7 +144,10 @@ def distribute_input(data: torch.Tensor | None, num_clusters: int):
         mean = data.double().mean(dim=0).float()
         var = (data.double().pow(2).mean(dim=0)
                - data.double().mean(dim=0).pow(2)).float()
-        return data, n, mean, var, seed_means_host(data, num_clusters)
+        seed_means, seed_idx = seed_fn(data)
+        if seed_info is not None:
+            seed_info["indices"] = seed_idx
+        return data, n, mean, var, seed_means
 
     if r == 0:
         if data is None or data.dim() != 2:
@@ -146,13 +160,18 @@ def distribute_input(data: torch.Tensor | None, num_clusters: int):
 
     k = num_clusters
     stats = torch.zeros(2 * d + k * d, dtype=torch.float32)
+    seed_idx = torch.zeros(k, dtype=torch.long)
     if r == 0:
         dmean = data.double().mean(dim=0)
         dvar = data.double().pow(2).mean(dim=0) - dmean * dmean
         stats[:d] = dmean.float()
         stats[d:2 * d] = dvar.float()
-        stats[2 * d:] = seed_means_host(data, k).reshape(-1)
+        seed_means, seed_idx = seed_fn(data)
+        stats[2 * d:] = seed_means.reshape(-1)
     broadcast_(stats)
+    if seed_info is not None:
+        broadcast_(seed_idx)
+        seed_info["indices"] = seed_idx
     mean, var = stats[:d], stats[d:2 * d]
     seed_means = stats[2 * d:].reshape(k, d)
 

@@ -81,6 +81,14 @@ class GmmConfig:
     # disables. Resume happens automatically when a checkpoint exists.
     checkpoint_dir: str | None = None
 
+    # Where the K0 starting means come from: "strided" = the reference's
+    # evenly-strided rows (gaussian.cu:108-123), which depend on the row
+    # order of the file; "kmeans++" = a greedy k-means++ draw over the full
+    # dataset (models.seed.seed_means_kmeanspp), reproducible from seed_rng.
+    # A checkpoint resume ignores both.
+    seed_method: str = "strided"
+    seed_rng: int = 0
+
     def validate(self) -> None:
         if not (1 <= self.num_clusters <= MAX_CLUSTERS):
             raise ValueError(
@@ -102,6 +110,13 @@ class GmmConfig:
         if self.mstep_precision not in ("fp32", "bf16x3"):
             raise ValueError(
                 f"mstep_precision must be fp32|bf16x3: {self.mstep_precision}")
+        if self.seed_method not in ("strided", "kmeans++"):
+            raise ValueError(
+                f"seed_method must be strided|kmeans++: {self.seed_method}")
+        if (isinstance(self.seed_rng, bool)
+                or not isinstance(self.seed_rng, int) or self.seed_rng < 0):
+            raise ValueError(
+                f"seed_rng must be an integer >= 0: {self.seed_rng!r}")
 
     @property
     def stop_number(self) -> int:
