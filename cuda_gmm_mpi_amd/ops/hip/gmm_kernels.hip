@@ -551,6 +551,102 @@ __device__ __forceinline__ float unfused_mulsub(float acc, float x, float y) {
   return acc - p;
 }
 
+// ---- the factor chain in registers, D <= 32 (wave 0 of the block) ----
+// The general chain below meets at a workgroup barrier after every column
+// and walks its sums through LDS; at D <= 32 one wave holds the whole
+// matrix, a row or column per lane, and neither is needed. Both halves are
+// right-looking: a finished value is applied at once to every element that
+// still waits for it, so the updates of one step are independent of each
+// other and only divide -> broadcast -> update is serial. Each element
+// still receives the same operations in the same kk order as in the general
+// chain, so the results are the same bits. DM is the unroll bound (register
+// arrays need static indices); steps at or past d are skipped by a uniform
+// branch, lanes and columns past d compute values nobody stores.
+__device__ __forceinline__ float lane_bcast(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+// Lower Cholesky of R in a [d*ldp] (lower triangle read), L written back
+// over it, diagonal included. Lane i owns row i.
+template <int DM>
+__device__ __forceinline__ void chol_regs(float* a, int d, int ldp) {
+  const int lane = threadIdx.x;
+  const bool alive = lane < d;
+  float* ri = a + (alive ? lane : 0) * ldp;
+  float w[DM];
+#pragma unroll
+  for (int m = 0; m < DM; ++m) w[m] = (alive && m <= lane) ? ri[m] : 0.0f;
+  // the pivot of row i is R[i][i] - sum_kk L[i][kk]^2 in kk order, kept as
+  // a running sum of its own and frozen once column i - 1 is done
+  float sd = alive ? ri[lane] : 0.0f;
+  const float lo = fmaf(1e-8f, fabsf(sd), 1e-30f);
+  float pv = sqrtf(fmaxf(sd, lo));
+#pragma unroll
+  for (int j = 0; j + 1 < DM; ++j) {
+    if (j + 1 >= d) continue;
+    const float l = w[j] / lane_bcast(pv, j);
+    if (lane > j) {
+      if (alive) ri[j] = l;
+      sd = fmaf(-l, l, sd);
+      pv = sqrtf(fmaxf(sd, lo));
+    }
+#pragma unroll
+    for (int m = j + 1; m < DM; ++m) w[m] = fmaf(-l, lane_bcast(l, m), w[m]);
+  }
+  if (alive) ri[lane] = pv;
+}
+
+// F = L^-1 (lower) by forward substitution, L read from a, F written to o.
+// Lane i owns column i and counts rows from its own diagonal: g[n] is
+// F[i+n][i], xv[n] its running sum. With that numbering the split of a sum
+// into fused head and unfused eights, (j - i) & 7 = n & 7 terms long, is the
+// same for every lane and known at compile time. L[i+n][i+t] differs per
+// lane, so it comes from LDS; none of those loads waits for the chain.
+template <int DM>
+__device__ __forceinline__ void inv_regs(const float* a, float* o, int d,
+                                         int ldp) {
+  const int lane = threadIdx.x;
+  const int i = lane < d ? lane : 0;
+  // lane's row i + n of L from column i on; rows past d read a[t], t < d
+  int off[DM];
+#pragma unroll
+  for (int n = 0; n < DM; ++n)
+    off[n] = (lane + n < d) ? (i + n) * ldp + i : 0;
+  // the sums start from a +0 the compiler cannot see through: from a
+  // literal it makes -p of 0 - p, which is -0 where the product is +0 (the
+  // rows of an identity R), and the general chain subtracts from a register
+  float zero = 0.0f;
+  asm("" : "+v"(zero));
+  float g[DM], xv[DM];
+#pragma unroll
+  for (int n = 0; n < DM; ++n) xv[n] = zero;
+  g[0] = 1.0f / a[off[0]];
+  if (lane < d) o[off[0]] = g[0];
+#pragma unroll
+  for (int t = 0; t + 1 < DM; ++t) {
+    if (t + 1 >= d) continue;
+#pragma unroll
+    for (int n = t + 1; n < DM; ++n) {
+      const float lv = a[off[n] + t];
+      xv[n] = (t < (n & 7)) ? fmaf(-lv, g[t], xv[n])
+                            : unfused_mulsub(xv[n], lv, g[t]);
+    }
+    g[t + 1] = xv[t + 1] / a[off[t + 1] + t + 1];
+    if (lane + t + 1 < d) o[off[t + 1]] = g[t + 1];
+  }
+}
+
+template <int DM>
+__device__ __forceinline__ void chain_regs(float* a, float* o, int d,
+                                           int ldp) {
+  chol_regs<DM>(a, d, ldp);
+  // lanes read what other lanes of this wave wrote: LDS serves one wave's
+  // accesses in order, the fence keeps the compiler from moving them
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  inv_regs<DM>(a, o, d, ldp);
+}
+
 // `a` is scratch LDS [d*ldp] for R, factored in place into L (only the
 // lower triangle is read); with r_global == nullptr the caller has put R
 // there already, barrier included. `o` [d*ldp] receives F (lower triangle
@@ -559,14 +655,14 @@ __device__ __forceinline__ float unfused_mulsub(float acc, float x, float y) {
 // Every element keeps the operations and the kk-ascending order of the
 // straightforward column Cholesky / forward substitution; what changed is
 // who computes them and how often the block meets at a barrier.
-__device__ inline void emit_mfac(float* a, float* o,
-                                 const float* __restrict__ r_global,
-                                 const float* __restrict__ means,
-                                 __hip_bfloat16* __restrict__ mfac,
-                                 float* __restrict__ mfac32, int c, int d,
-                                 const float* __restrict__ pi = nullptr,
-                                 float* __restrict__ constant = nullptr,
-                                 float* __restrict__ add = nullptr) {
+// (forced inline: as a call it takes runtime null checks and a stack frame)
+__device__ __forceinline__ void emit_mfac(
+    float* a, float* o, const float* __restrict__ r_global,
+    const float* __restrict__ means, __hip_bfloat16* __restrict__ mfac,
+    float* __restrict__ mfac32, int c, int d,
+    const float* __restrict__ pi = nullptr,
+    float* __restrict__ constant = nullptr,
+    float* __restrict__ add = nullptr) {
   const int tid = threadIdx.x;
   // odd LDS row stride: stride-d column walks with gcd(d, 32) > 1 put
   // whole lane groups on one bank (8-way at d = 24)
@@ -577,13 +673,25 @@ __device__ inline void emit_mfac(float* a, float* o,
       a[(t / d) * ldp + t % d] = r_global[(int64_t)c * d * d + t];
     __syncthreads();
   }
+  // D <= 32: wave 0 runs both halves of the chain in registers (above) and
+  // leaves L in a and F in o; the other waves wait for it here
+  const bool regs = d <= 32;
+  if (regs) {
+    if (tid < WAVE) {
+      if (d <= 8) chain_regs<8>(a, o, d, ldp);
+      else if (d <= 16) chain_regs<16>(a, o, d, ldp);
+      else if (d <= 24) chain_regs<24>(a, o, d, ldp);
+      else chain_regs<32>(a, o, d, ldp);
+    }
+    __syncthreads();
+  }
   // in-place lower Cholesky of R, one barrier per column. The pivot of
   // row i is R[i][i] - sum_kk L[i][kk]^2 in kk order: the row's owner
   // keeps that running sum in a register, subtracts each L[i][j] as it
   // produces it, and publishes the pivot together with L[i][i-1], one
   // column step before anyone reads it (a lone thread used to walk the
   // row through LDS for every pivot, between two barriers of its own).
-  {
+  if (!regs) {
     const bool own = tid < d;
     float* ri = a + tid * ldp;
     float sd = 0.0f, diag0 = 0.0f;
@@ -638,7 +746,7 @@ __device__ inline void emit_mfac(float* a, float* o,
   // The sum runs in kk order with the rounding the kernel has always had:
   // the first (j - i) % 8 terms as fused multiply-adds, the rest in eights
   // as a rounded product subtracted (unfused_mulsub keeps it that way).
-  if (tid < d) {
+  if (!regs && tid < d) {
     const int i = tid;
     for (int j = i; j < d; ++j) {
       const float* lj = a + j * ldp;

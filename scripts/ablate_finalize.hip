@@ -27,11 +27,27 @@ constexpr int NSTAMP = 9;
 static const char* kPhase[NSTAMP - 1] = {
     "pi + means", "R", "Cholesky", "ln det + constants", "inverse",
     "u0", "emission", "(tail barrier)"};
+// D <= 32: the chain runs first, as a whole, on wave 0
+static const char* kPhaseRegs[NSTAMP - 1] = {
+    "pi + means", "R", "Cholesky", "inverse", "barrier, ln det + c.",
+    "u0", "emission", "(tail barrier)"};
 
 #define STAMP(n)                                                         \
   do {                                                                   \
     if (threadIdx.x == 0) stamps[blockIdx.x * NSTAMP + (n)] = clock64(); \
   } while (0)
+
+// chain_regs with a stamp between its halves
+template <int DM>
+__device__ __forceinline__ void chain_regs_stamped(float* a, float* o, int d,
+                                                   int ldp,
+                                                   long long* stamps) {
+  chol_regs<DM>(a, d, ldp);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  STAMP(3);
+  inv_regs<DM>(a, o, d, ldp);
+}
 
 __global__ void __launch_bounds__(NT)
 finalize_emit_stamped(const float* __restrict__ packed,
@@ -103,7 +119,21 @@ finalize_emit_stamped(const float* __restrict__ packed,
   // ---- emit_mfac, r_global == nullptr ----
   const int tid = threadIdx.x;
   float* u0 = o + d * ldp;
-  {
+  const bool regs = d <= 32;
+  if (regs) {
+    // wave 0 (thread 0's wave) runs both halves of the chain in registers;
+    // stamps 3 and 4 are taken in emit_mfac's order for this path: Cholesky,
+    // inverse, then the barrier with ln det and the constants
+    if (tid < WAVE) {
+      if (d <= 8) chain_regs_stamped<8>(a, o, d, ldp, stamps);
+      else if (d <= 16) chain_regs_stamped<16>(a, o, d, ldp, stamps);
+      else if (d <= 24) chain_regs_stamped<24>(a, o, d, ldp, stamps);
+      else chain_regs_stamped<32>(a, o, d, ldp, stamps);
+      STAMP(4);
+    }
+    __syncthreads();
+  }
+  if (!regs) {
     const bool own = tid < d;
     float* ri = a + tid * ldp;
     float sd = 0.0f, diag0 = 0.0f;
@@ -128,7 +158,7 @@ finalize_emit_stamped(const float* __restrict__ packed,
       __syncthreads();
     }
   }
-  STAMP(3);
+  if (!regs) STAMP(3);
   {
     __shared__ float wsum_e[NT / WAVE];
     const int nw = (blockDim.x + WAVE - 1) / WAVE;
@@ -148,8 +178,8 @@ finalize_emit_stamped(const float* __restrict__ packed,
     }
     __syncthreads();
   }
-  STAMP(4);
-  if (tid < d) {
+  if (!regs) STAMP(4);
+  if (!regs && tid < d) {
     const int i = tid;
     for (int j = i; j < d; ++j) {
       const float* lj = a + j * ldp;
@@ -324,7 +354,8 @@ int main(int argc, char** argv) {
   }
   printf("in-kernel clock, mean over %d blocks: %.0f ticks\n", k, tot / k);
   for (int q = 0; q + 1 < gmm::NSTAMP; ++q)
-    printf("  %-20s %8.0f ticks  %5.1f %%\n", gmm::kPhase[q], ph[q] / k,
+    printf("  %-20s %8.0f ticks  %5.1f %%\n",
+           (d <= 32 ? gmm::kPhaseRegs : gmm::kPhase)[q], ph[q] / k,
            100.0 * ph[q] / tot);
   float cst0 = 0.0f;
   CK(hipMemcpy(&cst0, dc, 4, hipMemcpyDeviceToHost));
