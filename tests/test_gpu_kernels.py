@@ -431,7 +431,10 @@ def test_estep_fused_f32_matches_cpu(device):
 
 
 def test_fuzz_kernels_vs_cpu(device):
-    """Randomized shape fuzz: fused/big E-step + moments vs CPU reference."""
+    """Randomized shape fuzz of the moments kernels only (bf16x3 and fp32,
+    D below and above 31) vs the CPU reference; no E-step kernel runs
+    here. The big-D E-step kernels are held to float64 in
+    test_gpu_bigd_oracle.py."""
     from cuda_gmm_mpi_amd.ops import functional as F
     rng = np.random.default_rng(2024)
     for trial in range(12):
