@@ -4,6 +4,7 @@ data file with a saved model.
 MODEL is a .npz written by ``gmm ... --save-model`` or, chosen by its
 suffix, a .summary file (lossy: %.3f parameters). Writes OUTSTEM.labels,
 one line per event: ``label,max posterior,log-probability`` as %d,%f,%f.
+A model with a uniform background labels the events it assigns to it -1.
 
 Exit codes: 0 ok, 1 bad arguments, 2 unreadable INFILE (as ``gmm``),
 5 unreadable MODEL or a model / data dimension mismatch.
@@ -105,6 +106,7 @@ def main(argv=None) -> int:
                 "D": model.num_dimensions,
                 "log_likelihood": pred.log_likelihood,
                 "counts": pred.counts.tolist(),
+                "background_count": pred.background_count,
                 "device": device,
                 "seconds": elapsed,
             }, f, indent=2)

@@ -85,6 +85,20 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0, metavar="N",
                    help="random seed of --seed-method kmeans++ (same seed, "
                         "same starting means, whatever the world size)")
+    p.add_argument("--background", action="store_true",
+                   help="add a uniform background component over the data's "
+                        "bounding box for outliers (debris, doublets, "
+                        "off-scale events): they get label -1 and a last "
+                        "membership column instead of inflating a cluster")
+    p.add_argument("--background-init", type=float, default=0.01,
+                   metavar="P", help="background weight at switch-on")
+    p.add_argument("--background-warmup", type=int, default=5, metavar="W",
+                   help="plain EM iterations at the starting K before the "
+                        "background is switched on")
+    p.add_argument("--background-log-volume", type=float, default=None,
+                   metavar="X",
+                   help="ln of the background's volume (default: the "
+                        "bounding box of the data)")
     p.add_argument("--gpus", type=int, default=None,
                    help="spawn N single-GPU worker processes on this node "
                         "(one rank per GPU over RCCL)")
@@ -116,6 +130,9 @@ def config_from_args(args) -> GmmConfig:
         checkpoint_dir=args.checkpoint_dir,
         nearest_target=args.nearest_target,
         seed_method=args.seed_method, seed_rng=args.seed,
+        background=args.background, background_init=args.background_init,
+        background_warmup=args.background_warmup,
+        background_log_volume=args.background_log_volume,
     )
     cfg.validate()
     return cfg
@@ -167,7 +184,13 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
 
     # memberships first: recompute_memberships needs the saved means in the
     # engine's internally-centered frame, so it must run before de-centering
-    w_shard = engine.recompute_memberships(result.state)
+    # (K + 1 rows with a background, its own posterior last)
+    w_shard = engine.recompute_memberships(result.state,
+                                           result.background_pi)
+    background = None
+    if cfg.background:
+        background = {"pi": result.background_pi, "n": result.background_n,
+                      "log_volume": result.background_log_volume}
 
     # de-center the saved model for output. clone() is load-bearing: on CPU
     # .to("cpu") returns aliased tensors and the += would corrupt the saved
@@ -177,7 +200,10 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
     # the model keeps the internal-frame means: scoring the training data
     # with it then reproduces w_shard exactly
     model = GmmModel.from_state(result.state.to("cpu"), engine.center.cpu(),
-                                cfg.diag_only, cfg.bug_compat)
+                                cfg.diag_only, cfg.bug_compat,
+                                background_pi=result.background_pi,
+                                background_log_volume=(
+                                    result.background_log_volume))
     if save_model and rank == 0:
         model.save(save_model)
     memberships = None
@@ -194,12 +220,12 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                               w_shard.cpu().numpy())
         if rank == 0:
             gio.write_summary(outfile + ".summary", out_state,
-                              cfg.enable_output)
+                              cfg.enable_output, background)
     else:
         memberships = engine.gather_memberships(w_shard)
         if rank == 0:
             gio.write_summary(outfile + ".summary", out_state,
-                              cfg.enable_output)
+                              cfg.enable_output, background)
             if cfg.enable_output and write_results and memberships is not None:
                 gio.write_results(outfile + ".results", data, memberships)
 
@@ -224,6 +250,10 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
         "seed_method": cfg.seed_method,
         "seed_rng": cfg.seed_rng,
         "seed_indices": engine.seed_indices,
+        "background_pi": result.background_pi if cfg.background else None,
+        "background_n": result.background_n if cfg.background else None,
+        "background_log_volume": (result.background_log_volume
+                                  if cfg.background else None),
     }
 
 
@@ -255,6 +285,10 @@ def main(argv=None) -> int:
         cfg = config_from_args(args)
     except ValueError as e:
         print(str(e))
+        return 1
+    if args.background and args.scatter_input:
+        print("--background cannot be combined with --scatter-input "
+              "(the bounding box of the full data is not broadcast)\n")
         return 1
     if args.weights and args.scatter_input:
         print("--weights cannot be combined with --scatter-input "
@@ -356,6 +390,10 @@ def main(argv=None) -> int:
                     "seed_method": result["seed_method"],
                     "seed_rng": result["seed_rng"],
                     "seed_indices": result["seed_indices"],
+                    "background_pi": result["background_pi"],
+                    "background_n": result["background_n"],
+                    "background_log_volume":
+                        result["background_log_volume"],
                 }, f, indent=2)
         if rank == 0 and args.enable_print:
             print(f"Ideal clusters: {result['num_clusters']} "

@@ -43,6 +43,10 @@ class SweepResult:
     min_rissanen: float
     likelihood: float
     rissanen_by_k: dict[int, float]
+    # the uniform background of the saved model (zeros without one)
+    background_pi: float = 0.0
+    background_n: float = 0.0
+    background_log_volume: float = 0.0
 
 
 class EmEngine:
@@ -53,7 +57,8 @@ class EmEngine:
                  seed_means: torch.Tensor, var_per_dim: torch.Tensor,
                  device: torch.device | str = "cpu",
                  profile: Profile | None = None,
-                 weights_shard: torch.Tensor | None = None):
+                 weights_shard: torch.Tensor | None = None,
+                 background_log_volume: float | None = None):
         self.cfg = config
         self.device = torch.device(device)
         self.rank = pdist.rank()
@@ -123,10 +128,23 @@ class EmEngine:
         self.use_lds_estep = F.estep_fused_lds_available(
             self.device, config.estep_dtype, self.d, k0,
         )
-        if self.s is not None:
-            # the weights ride on the lse the M-step kernels subtract; the
-            # LDS variant writes posteriors and has no lse. The lse family
-            # handles any K.
+        # uniform background component (None / False: nothing below is
+        # allocated or dispatched differently)
+        self.background = bool(config.background)
+        if self.background:
+            lnv = (background_log_volume
+                   if background_log_volume is not None
+                   else config.background_log_volume)
+            if lnv is None:
+                raise ValueError(
+                    "a background fit needs the log volume of the full "
+                    "data: build the engine with build_engine or set "
+                    "background_log_volume")
+            self.bg_log_volume = float(lnv)
+        if self.s is not None or self.background:
+            # the weights and the background ride on the lse the M-step
+            # kernels subtract; the LDS variant writes posteriors and has
+            # no lse. The lse family handles any K.
             self.use_lds_estep = False
         self.use_big_estep = F.estep_big_available(
             self.device, config.estep_dtype, self.d,
@@ -177,6 +195,31 @@ class EmEngine:
         if self.s is not None and self.device.type == "cuda":
             # a separate buffer: _lse stays the normalizer of posteriors()
             self._lse_w = torch.empty_like(self._lse)
+        # background: device state [pi0, b, lik_add, n0], starting switched
+        # off (pi0 = 0 is a fixed point of the update, so warm-up is just
+        # "b is still -inf"), and the persistent partials the E-step leaves
+        # for the update of the NEXT iteration
+        self._bg: torch.Tensor | None = None
+        self._bg_partial: torch.Tensor | None = None
+        self._bg_n0: torch.Tensor | None = None   # world > 1: reduced n0
+        self._lse_b: torch.Tensor | None = None   # lse incl. the background
+        self._bg_on = False
+        self._bg_plain_iters = 0
+        if self.background:
+            self._bg = F.background_state(self.device)
+            self._bg_partial = F.background_partial(self.n_shard, self.device)
+            self._bg_n0 = torch.zeros(1, dtype=torch.float32,
+                                      device=self.device)
+            if self.device.type == "cuda":
+                if self._lse_w is None:
+                    # the lse the moments read IS lse_b; _lse stays the
+                    # Gaussian-only lse the E-step wrote
+                    self._lse_w = torch.empty_like(self._lse)
+                    self._lse_b = self._lse_w
+                else:
+                    self._lse_b = torch.empty_like(self._lse)
+            else:
+                self._lse_b = torch.empty(self.n_shard, dtype=torch.float32)
         self.epsilon = em_epsilon(self.d, self.n_total)
         self.likelihood = 0.0
         # hipGraph capture of the EM iteration (launch-overhead elimination);
@@ -275,8 +318,9 @@ class EmEngine:
         st = self.state.shrink(k)
         weighted = self.s is not None
         want_lik = need_lik
-        if weighted and self.device.type == "cuda":
-            # the event-weight kernel below produces the likelihood
+        if (weighted or self.background) and self.device.type == "cuda":
+            # the event-weight / background kernel below produces the
+            # likelihood
             need_lik = False
         with self.profile.time("e_step"):
             self._w_is_logw = False
@@ -329,20 +373,30 @@ class EmEngine:
                     self.x_estep, st.means, st.Rinv, st.constant, st.pi,
                     self.cfg.diag_only, out=self.w[:k],
                 )
-                if weighted:
+                if self.background:
+                    # w = exp(logw - lse_b): columns sum to 1 - r0; the
+                    # M-step reads it, times s in a weighted fit
+                    w, self._w_s, lik = F.estep_posteriors_background(
+                        logw, self._bg, self.s, self._lse_b,
+                        self._bg_partial)
+                elif weighted:
                     # w stays normalized; the M-step reads s * w
                     w, self._w_s, lik = F.estep_posteriors_weighted(
                         logw, self.s)
                 else:
                     w, lik = F.estep_posteriors(logw)
-            if weighted and self.device.type == "cuda":
+            if (weighted or self.background) and self.device.type == "cuda":
                 if not self._w_is_logw:
                     raise RuntimeError(
-                        "per-event weights need an E-step of the lse "
-                        "family (use_lds_estep must stay off)")
-                lik = F.event_weight_lse(self._lse, self.s, self._lns,
-                                         self._lse_w, want_lik,
-                                         lik_out=self._lik_dev)
+                        "per-event weights and the background need an "
+                        "E-step of the lse family (use_lds_estep must stay "
+                        "off)")
+                if self.background:
+                    lik = self._background_lse(want_lik)
+                else:
+                    lik = F.event_weight_lse(self._lse, self.s, self._lns,
+                                             self._lse_w, want_lik,
+                                             lik_out=self._lik_dev)
         self.profile.count("regroup")
         return lik
 
@@ -356,6 +410,72 @@ class EmEngine:
             pdist.all_reduce_(t)
             if t.data_ptr() != self._lik_dev.data_ptr():
                 self._lik_dev.copy_(t)
+        if self.background:
+            # ln L = sum lse_b + n_total ln(1 - pi0), pi0 the one this
+            # E-step ran with: one device add of the state's lik_add
+            self._lik_dev.add_(self._bg[2:3])
+
+    # ---------------------------------------------------------- background
+
+    def _background_lse(self, need_lik: bool) -> torch.Tensor | None:
+        """CUDA: background_lse over the current lse. Writes the lse the
+        moments read (weights folded in: it replaces event_weight_lse), the
+        n0 partials and, for a weighted fit, lse_b for posteriors()."""
+        lse_b = self._lse_b if self.s is not None else None
+        return F.background_lse(self._lse, self._bg, self.s, self._lns,
+                                self._lse_w, self._bg_partial, lse_b=lse_b,
+                                need_lik=need_lik, lik_out=self._lik_dev)
+
+    def _background_update(self) -> None:
+        """pi0 <- n0 / n_total from the previous E-step's partials, on the
+        device. World > 1: the shard sums are all-reduced first, one float."""
+        part = self._bg_partial[0]
+        if self.world > 1:
+            if self.device.type == "cuda":
+                from .ops.backend import hip_ext
+                hip_ext().reduce_scalar(part, self._bg_n0)
+            else:
+                self._bg_n0.copy_(part.sum().reshape(1))
+            with self.profile.time("comm"):
+                pdist.all_reduce_(self._bg_n0)
+            part = self._bg_n0
+        F.background_update(part, self.n_total, self.bg_log_volume, self._bg)
+
+    def _maybe_switch_on_background(self, k: int) -> bool:
+        """After the warm-up iterations: write (init, b(init)) into the
+        device state and redo the background pass over the current E-step,
+        so the next M-step already sees it. A device write plus one launch
+        between graph replays (the graphs read the state on the device).
+        Leaves the likelihood with the background in the device scalar."""
+        if (not self.background or self._bg_on
+                or self._bg_plain_iters < self.cfg.background_warmup):
+            return False
+        pi0 = float(self.cfg.background_init)
+        n0 = pi0 * float(self.n_total)
+        pi0, b, lik_add = F.background_update_host(n0, self.n_total,
+                                                   self.bg_log_volume)
+        self._bg.copy_(torch.tensor([pi0, b, lik_add, n0],
+                                    dtype=torch.float32))
+        self._bg_on = True
+        if self.device.type == "cuda":
+            lik = self._background_lse(True)
+        else:
+            # the CPU buffer holds posteriors, not log weights: redo the
+            # E-step (once per fit)
+            lik = self._estep(k)
+        self._finish_likelihood(lik)
+        return True
+
+    @property
+    def background_pi(self) -> float:
+        """pi0 of the current state (0.0 without a background)."""
+        return float(self._bg[0].item()) if self.background else 0.0
+
+    @property
+    def background_n(self) -> float:
+        """The background's share of the observations, pi0 * n_total-like:
+        the n0 the last update read."""
+        return float(self._bg[3].item()) if self.background else 0.0
 
     def _reduce_likelihood(self, lik_part: torch.Tensor) -> float:
         self._finish_likelihood(lik_part)
@@ -365,6 +485,10 @@ class EmEngine:
         """One EM iteration; with need_lik the reduced likelihood lands in
         the persistent device scalar."""
         self._mstep(k)
+        if self.background:
+            # between the M-step and the E-step: the pi0 of an E-step comes
+            # from the previous E-step's r0, like every other parameter
+            self._background_update()
         lik = self._estep(k, need_lik)
         if need_lik and lik is not None:
             self._finish_likelihood(lik)
@@ -457,9 +581,9 @@ class EmEngine:
             # discards it; the final model and likelihood are identical).
             self._estep(k, need_lik=False)
             for _ in range(max(0, cfg.min_iters - 1)):
-                self.em_iteration(k, need_lik=False)
+                self._em_step(k, need_lik=False)
             if cfg.min_iters >= 1:
-                self.em_iteration(k, need_lik=True)
+                self._em_step(k, need_lik=True)
             else:
                 self._finish_likelihood(self._estep(k))
             lik = float(self._lik_dev.item())
@@ -472,8 +596,13 @@ class EmEngine:
         while iters < cfg.min_iters or (
             abs(change) > self.epsilon and iters < cfg.max_iters
         ):
+            if self._maybe_switch_on_background(k):
+                # compare like with like: the likelihood jumps at switch-on
+                lik = float(self._lik_dev.item())
             old_lik = lik
             self.em_iteration(k)
+            if self.background and not self._bg_on:
+                self._bg_plain_iters += 1
             lik = float(self._lik_dev.item())
             change = lik - old_lik
             iters += 1
@@ -483,6 +612,14 @@ class EmEngine:
         self.likelihood = lik
         self.total_em_iterations += iters
         return lik
+
+    def _em_step(self, k: int, need_lik: bool = True) -> None:
+        """em_iteration with the background's warm-up bookkeeping: switch
+        it on before the iteration once enough plain ones have run."""
+        self._maybe_switch_on_background(k)
+        self.em_iteration(k, need_lik)
+        if self.background and not self._bg_on:
+            self._bg_plain_iters += 1
 
     def em_iteration(self, k: int, need_lik: bool = True) -> None:
         """One EM iteration: M-step + all-reduce + constants + E-step +
@@ -625,6 +762,7 @@ class EmEngine:
         best_k = k
         min_rissanen = float("inf")
         best_lik = 0.0
+        best_bg = (0.0, 0.0)   # (pi0, n0) of the saved model
         riss_by_k: dict[int, float] = {}
 
         if cfg.checkpoint_dir:
@@ -684,7 +822,8 @@ class EmEngine:
             # lazy-Rinv paths: make state.Rinv reference-faithful before
             # it is saved, merged, checkpointed or broadcast
             self._refresh_rinv(k)
-            riss = rissanen_score(lik, k, self.d, self.n_total)
+            riss = rissanen_score(lik, k, self.d, self.n_total,
+                                  extra_params=1 if self.background else 0)
             riss_by_k[k] = riss
             if cfg.enable_print and self.rank == 0:
                 print(f"\nRissanen Score: {riss:e}")
@@ -702,6 +841,7 @@ class EmEngine:
                 min_rissanen = riss
                 best_k = k
                 best_lik = lik
+                best_bg = (self.background_pi, self.background_n)
                 best_state = self.state.shrink(k).clone(with_memberships=False)
 
             if k <= stop:
@@ -759,24 +899,40 @@ class EmEngine:
             state=best_state, num_clusters=best_k,
             min_rissanen=min_rissanen, likelihood=best_lik,
             rissanen_by_k=riss_by_k,
+            background_pi=best_bg[0], background_n=best_bg[1],
+            background_log_volume=(self.bg_log_volume if self.background
+                                   else 0.0),
         )
 
     def posteriors(self, k: int) -> torch.Tensor:
         """Normalized posteriors [k, n_shard] for the current E-step state
         (paths that emit log weights normalize with the lse)."""
+        if self.background:
+            # K + 1 rows, the background's posterior last
+            b = self._bg[1]
+            r0 = torch.where(torch.isinf(b), torch.zeros_like(self._lse_b),
+                             torch.exp(b - self._lse_b))
+            w = self.w[:k]
+            if getattr(self, "_w_is_logw", False):
+                w = torch.exp(w - self._lse_b.unsqueeze(0))
+            return torch.cat([w, r0.unsqueeze(0)], dim=0)
         if self._lse is None or not getattr(self, "_w_is_logw", False):
             return self.w[:k]
         return torch.exp(self.w[:k] - self._lse.unsqueeze(0))
 
     # ------------------------------------------------------------- output
 
-    def recompute_memberships(self, saved: GmmState) -> torch.Tensor:
+    def recompute_memberships(self, saved: GmmState,
+                              background_pi: float | None = None
+                              ) -> torch.Tensor:
         """Shard posteriors [K, n_shard] for the saved best model.
 
         Memberships never leave their shard during the sweep; for the
         .results file they are regenerated from the saved parameters (the
         final E-step of the best K is a pure function of those parameters)
-        and gathered once.
+        and gathered once. A fit with a background returns K + 1 rows, the
+        background's last, for ``background_pi`` (default: the current
+        state's pi0; pass the saved model's).
         """
         k = saved.num_clusters
         st = saved.to(self.device)
@@ -784,6 +940,10 @@ class EmEngine:
             self.x_estep, st.means, st.Rinv, st.constant, st.pi,
             self.cfg.diag_only,
         )
+        if self.background:
+            pi0 = (self.background_pi if background_pi is None
+                   else float(background_pi))
+            return F.background_posteriors(logw, pi0, self.bg_log_volume)
         w, _ = F.estep_posteriors(logw)
         return w
 
@@ -866,10 +1026,18 @@ def build_engine(data_by_event: np.ndarray | torch.Tensor, config: GmmConfig,
             seed_idx = torch.zeros(k, dtype=torch.long)
         pdist.broadcast_(seed_means)
         pdist.broadcast_(seed_idx)
+    lnv = None
+    if config.background:
+        # from the FULL data (every rank has it), so the volume and with it
+        # the fit do not depend on the world size
+        lnv = (config.background_log_volume
+               if config.background_log_volume is not None
+               else F.background_log_volume(data, sw))
     engine = EmEngine(
         data[s:e], config, n, center, seed_means, var.float(),
         device=device, profile=profile,
         weights_shard=None if sw is None else sw[s:e].float(),
+        background_log_volume=lnv,
     )
     engine.seed_indices = [int(i) for i in seed_idx]
     return engine
@@ -940,6 +1108,11 @@ def build_engine_sharded(shard: torch.Tensor, config: GmmConfig,
             "per-event weights are not supported with scattered input "
             "(--scatter-input): every rank must read the weights file; "
             "use the shared-filesystem path (build_engine)")
+    if config.background:
+        raise ValueError(
+            "a background component is not supported with scattered input "
+            "(--scatter-input): the bounding box of the full data is not "
+            "broadcast; use the shared-filesystem path (build_engine)")
     config.validate()
     d = shard.shape[1]
     center = mean.float() if config.center_data else torch.zeros(d)

@@ -23,20 +23,27 @@ from ..ops import functional as F
 from .state import GmmState
 
 FORMAT_VERSION = 1
+# a model with a uniform background component: version 1 plus two scalars
+FORMAT_VERSION_BACKGROUND = 2
 
 _ARRAYS = ("center", "means_centered", "pi", "N", "constant", "avgvar",
            "R", "Rinv")
 _FLAGS = ("diag_only", "bug_compat")
 _KEYS = ("format_version",) + _ARRAYS + _FLAGS
+_BACKGROUND = ("background_pi", "background_log_volume")
+_KEYS_BY_VERSION = {FORMAT_VERSION: _KEYS,
+                    FORMAT_VERSION_BACKGROUND: _KEYS + _BACKGROUND}
 
 
 @dataclasses.dataclass
 class Prediction:
-    labels: np.ndarray         # int32 [N], first argmax of the posteriors
+    labels: np.ndarray         # int32 [N], first argmax of the posteriors;
+    #                            -1 = the background (models that have one)
     log_prob: np.ndarray       # fp32 [N], ln p(x_e)
-    max_posterior: np.ndarray  # fp32 [N], posterior of the assigned cluster
+    max_posterior: np.ndarray  # fp32 [N], posterior of the assigned component
     log_likelihood: float      # float64 sum of log_prob
-    counts: np.ndarray         # int64 [K], events per label
+    counts: np.ndarray         # int64 [K], events per cluster label
+    background_count: int = 0  # events labelled -1
 
 
 def _as_events(data) -> torch.Tensor:
@@ -64,6 +71,11 @@ class GmmModel:
     Rinv: torch.Tensor            # [K, D, D]
     diag_only: bool = False
     bug_compat: bool = True
+    # uniform background: the mixture is (1 - background_pi) * sum_c pi_c
+    # N_c + background_pi / V, ln V = background_log_volume; pi stays
+    # normalised among the clusters. background_pi == 0: no background.
+    background_pi: float = 0.0
+    background_log_volume: float = 0.0
 
     def __post_init__(self):
         for name in _ARRAYS:
@@ -71,6 +83,8 @@ class GmmModel:
                     .detach().to("cpu", torch.float32).contiguous())
         self.diag_only = bool(self.diag_only)
         self.bug_compat = bool(self.bug_compat)
+        self.background_pi = float(self.background_pi)
+        self.background_log_volume = float(self.background_log_volume)
         self._validate()
 
     def _validate(self) -> None:
@@ -81,6 +95,12 @@ class GmmModel:
                 "avgvar": (k,), "R": (k, d, d), "Rinv": (k, d, d)}
         if k < 1 or d < 1:
             raise ValueError(f"model needs K >= 1 and D >= 1, got {k}x{d}")
+        if not (0.0 <= self.background_pi < 1.0
+                and np.isfinite(self.background_log_volume)):
+            raise ValueError(
+                f"inconsistent model: background_pi {self.background_pi} "
+                f"must be in [0, 1) and background_log_volume "
+                f"{self.background_log_volume} finite")
         for name, shape in want.items():
             got = tuple(getattr(self, name).shape)
             if got != shape:
@@ -97,6 +117,10 @@ class GmmModel:
         return int(self.means_centered.shape[1])
 
     @property
+    def has_background(self) -> bool:
+        return self.background_pi > 0.0
+
+    @property
     def means(self) -> torch.Tensor:
         """Cluster means in the data's own frame."""
         return self.means_centered + self.center.unsqueeze(0)
@@ -106,18 +130,22 @@ class GmmModel:
     @classmethod
     def from_state(cls, state: GmmState, center: torch.Tensor,
                    diag_only: bool = False,
-                   bug_compat: bool = True) -> "GmmModel":
+                   bug_compat: bool = True, background_pi: float = 0.0,
+                   background_log_volume: float = 0.0) -> "GmmModel":
         """From an engine state whose means are in the centred frame."""
         return cls(center=center.clone(), means_centered=state.means.clone(),
                    pi=state.pi.clone(), N=state.N.clone(),
                    constant=state.constant.clone(),
                    avgvar=state.avgvar.clone(), R=state.R.clone(),
                    Rinv=state.Rinv.clone(), diag_only=diag_only,
-                   bug_compat=bug_compat)
+                   bug_compat=bug_compat, background_pi=background_pi,
+                   background_log_volume=(background_log_volume
+                                          if background_pi > 0.0 else 0.0))
 
     @classmethod
     def from_params(cls, means, R, pi, N=None, center=None,
-                    diag_only: bool = False) -> "GmmModel":
+                    diag_only: bool = False, background_pi: float = 0.0,
+                    background_log_volume: float = 0.0) -> "GmmModel":
         """From means [K, D] (data frame), covariances and weights; Rinv and
         constant come from cpu_reference.compute_constants (natural log).
         The default centre is the pi-weighted mean of the means."""
@@ -134,7 +162,9 @@ class GmmModel:
                    pi=pi, N=(torch.as_tensor(N, dtype=torch.float32)
                              if N is not None else torch.zeros(k)),
                    constant=constant, avgvar=torch.zeros(k), R=r, Rinv=rinv,
-                   diag_only=diag_only, bug_compat=False)
+                   diag_only=diag_only, bug_compat=False,
+                   background_pi=background_pi,
+                   background_log_volume=background_log_volume)
 
     @classmethod
     def from_summary(cls, path: str) -> "GmmModel":
@@ -146,17 +176,33 @@ class GmmModel:
         exactly."""
         from ..utils.io import read_summary
         s = read_summary(path)
-        return cls.from_params(s["means"], s["R"], s["pi"], N=s["N"])
+        pi0 = float(s.get("background_pi", 0.0))
+        if pi0 <= 0.0:
+            return cls.from_params(s["means"], s["R"], s["pi"], N=s["N"])
+        # the cluster lines hold (1 - pi0) * pi_c: back to pi_c, normalised
+        # among the clusters
+        pi = s["pi"].astype(np.float64) / (1.0 - pi0)
+        return cls.from_params(
+            s["means"], s["R"], pi.astype(np.float32), N=s["N"],
+            background_pi=pi0,
+            background_log_volume=float(s["background_log_volume"]))
 
     # ------------------------------------------------------------- save/load
 
     def save(self, path: str) -> None:
-        """One .npz, every field fp32, written atomically."""
-        payload = {"format_version": np.float32(FORMAT_VERSION)}
+        """One .npz, every field fp32, written atomically. A model without
+        a background writes format version 1, one with it version 2 (the
+        two background scalars added, as float64)."""
+        version = (FORMAT_VERSION_BACKGROUND if self.has_background
+                   else FORMAT_VERSION)
+        payload = {"format_version": np.float32(version)}
         for name in _ARRAYS:
             payload[name] = getattr(self, name).numpy()
         for name in _FLAGS:
             payload[name] = np.float32(getattr(self, name))
+        if self.has_background:
+            for name in _BACKGROUND:
+                payload[name] = np.float64(getattr(self, name))
         # np.savez appends .npz when missing — keep the suffix on the temp name
         tmp = f"{path}.tmp.{os.getpid()}.npz"
         np.savez(tmp, **payload)
@@ -172,28 +218,35 @@ class GmmModel:
         try:
             with np.load(path, allow_pickle=False) as z:
                 have = set(z.files)
-                if have != set(_KEYS):
-                    missing = sorted(set(_KEYS) - have)
-                    extra = sorted(have - set(_KEYS))
+                # the key set is strict per format version
+                version = (float(np.asarray(z["format_version"]))
+                           if "format_version" in have else FORMAT_VERSION)
+                keys = _KEYS_BY_VERSION.get(version, _KEYS)
+                if have != set(keys):
+                    missing = sorted(set(keys) - have)
+                    extra = sorted(have - set(keys))
                     raise ValueError(
                         f"not a GmmModel file: missing keys {missing}, "
                         f"unexpected keys {extra}")
-                fields = {name: np.asarray(z[name]) for name in _KEYS}
+                fields = {name: np.asarray(z[name]) for name in keys}
         except ValueError as e:
             raise ValueError(f"cannot load model {path}: {e}") from None
         except Exception as e:  # noqa: BLE001 — truncated / not a zip
             raise ValueError(
                 f"cannot load model {path}: unreadable .npz ({e})") from None
         version = float(fields["format_version"])
-        if version != FORMAT_VERSION:
+        if version not in _KEYS_BY_VERSION:
             raise ValueError(f"cannot load model {path}: format version "
-                             f"{version:g}, this build reads {FORMAT_VERSION}")
+                             f"{version:g}, this build reads "
+                             f"{sorted(_KEYS_BY_VERSION)}")
+        background = {name: float(fields[name]) for name in _BACKGROUND
+                      if name in fields}
         try:
             return cls(**{name: torch.from_numpy(
                               fields[name].astype(np.float32))
                           for name in _ARRAYS},
                        diag_only=bool(fields["diag_only"]),
-                       bug_compat=bool(fields["bug_compat"]))
+                       bug_compat=bool(fields["bug_compat"]), **background)
         except ValueError as e:
             raise ValueError(f"cannot load model {path}: {e}") from None
 
@@ -284,13 +337,39 @@ class GmmModel:
                 lab, lse, pmax = cpu.classify(
                     self._stage(chunk, center, estep_dtype), st.means,
                     st.Rinv, st.constant, st.pi, self.diag_only)
+            if self.has_background:
+                lab, lse, pmax = self._background_pass(lab, lse, pmax)
             labels[s:e] = lab.cpu().numpy()
             log_prob[s:e] = lse.cpu().numpy()
             max_post[s:e] = pmax.cpu().numpy()
         return Prediction(
             labels=labels, log_prob=log_prob, max_posterior=max_post,
             log_likelihood=float(log_prob.astype(np.float64).sum()),
-            counts=np.bincount(labels, minlength=k).astype(np.int64))
+            counts=np.bincount(labels[labels >= 0],
+                               minlength=k).astype(np.int64),
+            background_count=int((labels < 0).sum()))
+
+    def _background_pass(self, lab: torch.Tensor, lse: torch.Tensor,
+                         pmax: torch.Tensor
+                         ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The background on top of a Gaussian-only classification, from its
+        12 bytes per event alone (a few elementwise ops; predict is bound by
+        the host-to-device copy): with lse_b = logaddexp(lse, b) the
+        background's posterior is r0 = exp(b - lse_b) and the largest
+        cluster posterior pmax * exp(lse - lse_b) (the largest log-weight is
+        lse + ln pmax). Label -1 where r0 is strictly the larger — or where
+        the event is so far out that no cluster posterior is a number;
+        log_prob = ln(1 - pi0) + lse_b."""
+        _, b, _ = cpu.background_update(self.background_pi, 1.0,
+                                        self.background_log_volume)
+        bt = torch.full_like(lse, b)
+        lse_b = torch.logaddexp(lse, bt)
+        r0 = torch.exp(bt - lse_b)
+        g = pmax * torch.exp(lse - lse_b)
+        is_bg = ~(r0 <= g)
+        lab = torch.where(is_bg, torch.full_like(lab, -1), lab)
+        pmax = torch.where(is_bg, r0, g)
+        return lab, lse_b + float(np.log1p(-self.background_pi)), pmax
 
     def score(self, data, device=None, estep_dtype: str = "fp32",
               chunk_events: int = 1 << 22) -> float:
@@ -302,11 +381,13 @@ class GmmModel:
                    chunk_events: int = 1 << 22) -> np.ndarray:
         """Full posterior matrix [K, N] (fp32), for .results-style output:
         per chunk the same ops EmEngine.recompute_memberships runs, so the
-        training data gives the training run's memberships."""
+        training data gives the training run's memberships. A model with a
+        background returns [K + 1, N], the background's row last."""
         x = self._check_data(data)
         dev = self._device(device)
         n = x.shape[0]
-        out = np.empty((self.num_clusters, n), dtype=np.float32)
+        rows = self.num_clusters + (1 if self.has_background else 0)
+        out = np.empty((rows, n), dtype=np.float32)
         st = self._on(dev)
         center = self.center.to(dev)
         for s in range(0, n, chunk_events):
@@ -314,6 +395,10 @@ class GmmModel:
             z = self._stage(x[s:e].to(dev), center, estep_dtype)
             logw = F.estep_logw(z, st.means, st.Rinv, st.constant, st.pi,
                                 self.diag_only)
-            w, _ = F.estep_posteriors(logw)
+            if self.has_background:
+                w = F.background_posteriors(logw, self.background_pi,
+                                            self.background_log_volume)
+            else:
+                w, _ = F.estep_posteriors(logw)
             out[:, s:e] = w.cpu().numpy()
         return out

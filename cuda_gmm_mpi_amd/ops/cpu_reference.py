@@ -94,6 +94,70 @@ def estep_posteriors_weighted(logw: torch.Tensor, s: torch.Tensor
     return w, w_s, lik
 
 
+def background_lse(lse: torch.Tensor, b: float,
+                   s: torch.Tensor | None = None
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                              torch.Tensor]:
+    """CPU twin of the background kernel for the mixture
+    (1 - pi0) sum_c pi_c N_c + pi0 / V with b = ln(pi0 / (1 - pi0)) - ln V:
+    (lse_b, lse_m, n0, lik), fp32.
+
+    lse_b = logaddexp(lse, b) (b = -inf: lse itself; both -inf: -inf);
+    lse_m is what the M-step subtracts: lse_b, or with weights s
+    event_weight_lse of lse_b (lse_b - ln s, +inf at s == 0);
+    n0 = sum_e s_e r0_e with r0 = exp(b - lse_b) the background posterior
+    and lik = sum_e s_e lse_b_e, zero-weight events skipped."""
+    b = float(b)
+    if b == float("-inf"):
+        lse_b = lse.clone()
+        r0 = torch.zeros_like(lse)
+    else:
+        bt = torch.full_like(lse, b)
+        hi = torch.maximum(lse, bt)
+        lse_b = hi + torch.log1p(torch.exp(-(lse - bt).abs()))
+        r0 = torch.exp(bt - lse_b)
+    if s is None:
+        return lse_b, lse_b, r0.sum(), lse_b.sum()
+    lse_m, lik = event_weight_lse(lse_b, s, torch.log(s))
+    n0 = torch.where(s == 0, torch.zeros_like(r0), s * r0).sum()
+    return lse_b, lse_m, n0, lik
+
+
+def background_update(n0: float, n_total: float, log_volume: float
+                      ) -> tuple[float, float, float]:
+    """(pi0, b, lik_add) of the background after an E-step that gave the
+    background n0 of n_total observations: pi0 = min(n0 / n_total,
+    1 - 1e-6), b = ln pi0 - ln(1 - pi0) - ln V (-inf at pi0 == 0) and
+    lik_add = n_total ln(1 - pi0), the term that completes
+    ln L = sum lse_b + lik_add. Float64 scalars (the kernel's own tail)."""
+    pi0 = float(n0) / float(n_total)
+    if not pi0 > 0.0:
+        pi0 = 0.0
+    pi0 = min(pi0, 1.0 - 1e-6)
+    l1m = math.log1p(-pi0)
+    b = (math.log(pi0) - l1m - float(log_volume)) if pi0 > 0.0 \
+        else float("-inf")
+    return pi0, b, float(n_total) * l1m
+
+
+def estep_posteriors_background(logw: torch.Tensor, b: float,
+                                s: torch.Tensor | None = None
+                                ) -> tuple[torch.Tensor, torch.Tensor | None,
+                                           torch.Tensor, torch.Tensor,
+                                           torch.Tensor]:
+    """E-step of a fit with a background: (w [K, N] = exp(logw - lse_b), the
+    Gaussian posteriors — their columns sum to 1 - r0 —, w_s = w * s for
+    the M-step of a weighted fit (else None), lse_b [N], n0, lik)."""
+    lse = estep_lse(logw)
+    lse_b, _, n0, lik = background_lse(lse, b, s)
+    w = torch.exp(logw - lse_b.unsqueeze(0))
+    w_s = None
+    if s is not None:
+        w_s = torch.where((s == 0).unsqueeze(0), torch.zeros_like(w),
+                          w * s.unsqueeze(0))
+    return w, w_s, lse_b, n0, lik
+
+
 def classify(x: torch.Tensor, means: torch.Tensor, rinv: torch.Tensor,
              constant: torch.Tensor, pi: torch.Tensor,
              diag_only: bool = False

@@ -96,6 +96,137 @@ def event_weight_lse(lse: torch.Tensor, s: torch.Tensor, lns: torch.Tensor,
     return lik
 
 
+def background_state(device) -> torch.Tensor:
+    """The 4-float device state of a background component, switched off:
+    [pi0, b, lik_add, n0] = [0, -inf, 0, 0] (pi0 = 0 is a fixed point)."""
+    return torch.tensor([0.0, float("-inf"), 0.0, 0.0], dtype=torch.float32,
+                        device=device)
+
+
+def background_partial(n: int, device) -> torch.Tensor:
+    """The persistent partial buffer of background_lse for n events: CUDA
+    [2, blocks] (row 0 the n0 partials, row 1 the likelihood's); CPU [2, 1]
+    holding the two sums themselves."""
+    dev = torch.device(device)
+    blocks = (int(hip_ext().event_weight_lse_blocks(n))
+              if dev.type == "cuda" else 1)
+    return torch.zeros((2, blocks), dtype=torch.float32, device=dev)
+
+
+def background_lse(lse: torch.Tensor, bg: torch.Tensor,
+                   s: torch.Tensor | None, lns: torch.Tensor | None,
+                   lse_m: torch.Tensor, partial: torch.Tensor,
+                   lse_b: torch.Tensor | None = None, need_lik: bool = True,
+                   lik_out: torch.Tensor | None = None
+                   ) -> torch.Tensor | None:
+    """Uniform background on the lse family. ``bg`` is background_state
+    (bg[1] = b is read on the device, so a captured graph follows it);
+    writes lse_m [N], the lse the lse-aware M-step kernels read (lse_b =
+    logaddexp(lse, b), shifted by -ln s and +inf at s == 0 with weights: it
+    replaces event_weight_lse), lse_b itself when a buffer is given, and the
+    n0 partials into ``partial`` (background_partial). With ``need_lik``
+    returns sum_e s_e lse_b_e reduced into ``lik_out`` [1] when given.
+    ``lse`` is left untouched. CPU tensors: the cpu_reference twin."""
+    if not lse.is_cuda:
+        lb, lm, n0, lik = cpu.background_lse(lse, float(bg[1]), s)
+        lse_m.copy_(lm)
+        if lse_b is not None:
+            lse_b.copy_(lb)
+        partial[0, 0] = n0
+        if not need_lik:
+            return None
+        partial[1, 0] = lik
+        out = lik_out if lik_out is not None else lse.new_empty(1)
+        out.copy_(lik.reshape(1))
+        return out
+    ext = hip_ext()
+    empty = lse.new_empty(0)
+    ext.background_lse(lse, bg, s if s is not None else empty,
+                       lns if s is not None else empty, lse_m,
+                       lse_b if lse_b is not None else empty,
+                       partial if need_lik else partial[0])
+    if not need_lik:
+        return None
+    lik = (lik_out if lik_out is not None
+           else torch.empty(1, dtype=torch.float32, device=lse.device))
+    ext.reduce_scalar(partial[1], lik)
+    return lik
+
+
+def background_update(n0_part: torch.Tensor, n_total: float,
+                      log_volume: float, bg: torch.Tensor) -> None:
+    """bg <- [pi0, b, lik_add, n0] from the n0 partials (contract:
+    cpu_reference.background_update); one block on CUDA, no host sync."""
+    if not bg.is_cuda:
+        n0 = n0_part.sum()
+        pi0, b, lik_add = cpu.background_update(float(n0), n_total,
+                                                log_volume)
+        bg.copy_(torch.tensor([pi0, b, lik_add, float(n0)],
+                              dtype=torch.float64))
+        return
+    hip_ext().background_update(n0_part, int(n0_part.numel()),
+                                float(n_total), float(log_volume), bg)
+
+
+background_update_host = cpu.background_update
+
+
+def estep_posteriors_background(logw: torch.Tensor, bg: torch.Tensor,
+                                s: torch.Tensor | None,
+                                lse_b: torch.Tensor, partial: torch.Tensor
+                                ) -> tuple[torch.Tensor,
+                                           torch.Tensor | None, torch.Tensor]:
+    """CPU engine path of a fit with a background: logw becomes
+    exp(logw - lse_b) in place (the Gaussian posteriors); lse_b and the n0
+    of ``partial`` are filled; returns (w, w * s for the M-step of a
+    weighted fit or None, likelihood sum_e s_e lse_b_e)."""
+    w, w_s, lb, n0, lik = cpu.estep_posteriors_background(
+        logw, float(bg[1]), s)
+    logw.copy_(w)
+    lse_b.copy_(lb)
+    partial[0, 0] = n0
+    partial[1, 0] = lik
+    return logw, w_s, lik
+
+
+def background_log_volume(data, weights=None) -> float:
+    """ln V of the bounding box of ``data`` [N, D]: float64
+    sum_d ln(max_d - min_d) over the events with weight > 0 (all without
+    weights). ValueError naming the dimension when a range is zero."""
+    x = torch.as_tensor(data).double()
+    if weights is not None:
+        x = x[torch.as_tensor(weights).reshape(-1) > 0]
+    if x.shape[0] == 0:
+        raise ValueError("background volume: no event with weight > 0")
+    rng = x.max(dim=0).values - x.min(dim=0).values
+    bad = torch.nonzero(~(rng > 0)).reshape(-1)
+    if bad.numel():
+        raise ValueError(
+            f"background volume: dimension {int(bad[0])} has zero range "
+            f"(give background_log_volume explicitly)")
+    return float(torch.log(rng).sum())
+
+
+def background_posteriors(logw: torch.Tensor, pi0: float,
+                          log_volume: float) -> torch.Tensor:
+    """[K + 1, N] posteriors of a mixture with a background from the
+    Gaussian log-weights (output path: the lse kernel or its CPU twin, then
+    a few torch ops): rows 0..K-1 exp(logw - lse_b), the last row
+    r0 = exp(b - lse_b)."""
+    if logw.is_cuda:
+        lse = torch.empty(logw.shape[1], dtype=torch.float32,
+                          device=logw.device)
+        estep_lse(logw, lse, need_lik=False)
+    else:
+        lse = cpu.estep_lse(logw)
+    _, b, _ = cpu.background_update(pi0, 1.0, log_volume)
+    bt = torch.full_like(lse, b)
+    lse_b = torch.logaddexp(lse, bt)
+    r0 = torch.exp(bt - lse_b) if b != float("-inf") else torch.zeros_like(lse)
+    return torch.cat([torch.exp(logw - lse_b.unsqueeze(0)),
+                      r0.unsqueeze(0)], dim=0)
+
+
 def estep_posteriors_weighted(logw: torch.Tensor, s: torch.Tensor
                               ) -> tuple[torch.Tensor, torch.Tensor,
                                          torch.Tensor]:

@@ -177,6 +177,74 @@ void event_weight_lse(torch::Tensor lse, torch::Tensor s, torch::Tensor lns,
   HIP_CHECK(hipGetLastError());
 }
 
+// background_lse: the geometry of event_weight_lse (one block per 4 * kNT
+// events, capped). `bg` is the 4-float background state (bg[1] = b is read
+// on the device); s / lns empty: unweighted; lse_b empty: not stored;
+// partial is [blocks] (n0 only) or [2 * blocks] (n0, then the likelihood).
+void background_lse(torch::Tensor lse, torch::Tensor bg, torch::Tensor s,
+                    torch::Tensor lns, torch::Tensor lse_m,
+                    torch::Tensor lse_b, torch::Tensor partial) {
+  check_f32(lse, "lse");
+  check_f32(bg, "bg");
+  check_f32(s, "s");
+  check_f32(lns, "lns");
+  check_f32(lse_m, "lse_m");
+  check_f32(lse_b, "lse_b");
+  check_f32(partial, "partial");
+  const int64_t n = lse.numel();
+  TORCH_CHECK(n >= 1, "empty lse");
+  TORCH_CHECK(bg.numel() == 4, "bg must be the 4-float background state");
+  const bool weighted = s.numel() > 0;
+  TORCH_CHECK(lse_m.numel() == n, "lse_m must be [N] like lse");
+  TORCH_CHECK((!weighted && lns.numel() == 0) ||
+                  (s.numel() == n && lns.numel() == n),
+              "s and lns must both be empty or [N] like lse");
+  TORCH_CHECK(lse_b.numel() == 0 || lse_b.numel() == n,
+              "lse_b must be empty or [N] like lse");
+  const int64_t grid = event_weight_lse_blocks(n);
+  TORCH_CHECK(partial.numel() == grid || partial.numel() == 2 * grid,
+              "partial must be [blocks] or [2 * blocks], blocks = "
+              "event_weight_lse_blocks(N)");
+  auto aligned = [](const torch::Tensor& t) {
+    return t.numel() == 0 ||
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  const int64_t nvec = (aligned(lse) && aligned(s) && aligned(lns) &&
+                        aligned(lse_m) && aligned(lse_b)) ? n / EW_VEC : 0;
+  float* pp = partial.data_ptr<float>();
+  float* lik_part = partial.numel() == 2 * grid ? pp + grid : nullptr;
+  float* lbp = lse_b.numel() ? lse_b.data_ptr<float>() : nullptr;
+  if (weighted) {
+    hipLaunchKernelGGL(gmm::background_lse_kernel<true>,
+                       dim3((unsigned)grid), dim3(kNT), 0, stream(),
+                       lse.data_ptr<float>(), bg.data_ptr<float>(),
+                       s.data_ptr<float>(), lns.data_ptr<float>(),
+                       lse_m.data_ptr<float>(), lbp, pp, lik_part, nvec, n);
+  } else {
+    hipLaunchKernelGGL(gmm::background_lse_kernel<false>,
+                       dim3((unsigned)grid), dim3(kNT), 0, stream(),
+                       lse.data_ptr<float>(), bg.data_ptr<float>(),
+                       (const float*)nullptr, (const float*)nullptr,
+                       lse_m.data_ptr<float>(), lbp, pp, lik_part, nvec, n);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// bg <- (pi0, b, lik_add, n0) from the first `nparts` entries of n0_part.
+void background_update(torch::Tensor n0_part, int64_t nparts, double n_total,
+                       double ln_v, torch::Tensor bg) {
+  check_f32(n0_part, "n0_part");
+  check_f32(bg, "bg");
+  TORCH_CHECK(bg.numel() == 4, "bg must be the 4-float background state");
+  TORCH_CHECK(nparts >= 1 && nparts <= n0_part.numel(),
+              "nparts must be in 1..n0_part.numel()");
+  TORCH_CHECK(n_total > 0.0, "n_total must be positive");
+  hipLaunchKernelGGL(gmm::background_update_kernel, dim3(1), dim3(kNT), 0,
+                     stream(), n0_part.data_ptr<float>(), nparts, n_total,
+                     ln_v, bg.data_ptr<float>());
+  HIP_CHECK(hipGetLastError());
+}
+
 template <typename T>
 void mstep_cov_impl(const torch::Tensor& x, const torch::Tensor& w,
                     const torch::Tensor& lse, torch::Tensor& partials) {
@@ -1046,6 +1114,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "lse_w = lse - ln s (+inf at s == 0) + weighted likelihood partials");
   m.def("event_weight_lse_blocks", &event_weight_lse_blocks,
         "block (= likelihood partial) count of event_weight_lse for N events");
+  m.def("background_lse", &background_lse,
+        "uniform background: lse_b = logaddexp(lse, b), the moments' lse_m, "
+        "block partials of n0 and (optionally) the likelihood");
+  m.def("background_update", &background_update,
+        "background state (pi0, b, lik_add, n0) from the n0 partials");
   m.def("mstep_covariance_partials", &mstep_covariance_partials,
         "packed weighted second-moment partials [nchunk,K,P]");
   m.def("constants", &constants,

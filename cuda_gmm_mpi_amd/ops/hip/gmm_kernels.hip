@@ -306,6 +306,130 @@ event_weight_lse_kernel(const float* __restrict__ lse,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Uniform background component: the mixture (1 - pi0) sum_c pi_c N_c + pi0/V
+// rides on the same contract. With b = ln(pi0 / (1 - pi0)) - ln V read from
+// the device scalar bg[1] (so a captured graph follows its updates):
+//   lse_b[e] = logaddexp(lse[e], b)   (b = -inf: lse_b == lse bit for bit;
+//                                      both -inf: -inf)
+//   r0[e]    = exp(b - lse_b[e])      background posterior (0 at b = -inf)
+//   lse_m[e] = lse_b[e]               what the moments kernels then read
+// With weights (W) it replaces event_weight_lse_kernel in the chain instead
+// of following it: lse_m = lse_b - lns, +inf where s == 0 (bitwise that
+// kernel applied to lse_b). lse_b is also stored when `lse_b` is non-null
+// (a weighted fit needs it to normalise posteriors for output).
+// Block partials: n0_part[blockIdx.x] = sum s_e r0_e on every call, and
+// lik_part[blockIdx.x] = sum s_e lse_b_e when `lik_part` is non-null
+// (zero-weight events skipped in both). Same geometry, vector / tail split
+// and fixed summation order as event_weight_lse_kernel: deterministic.
+// The accurate expf / log1pf (not the fast intrinsics): the correction term
+// log1p(exp(-|lse - b|)) <= ln 2 is the whole effect at small pi0.
+// ---------------------------------------------------------------------------
+template <bool W>
+__device__ __forceinline__ float background_one(float l, float b, float s,
+                                                float ls, float* lb_out,
+                                                float* n0, float* lik) {
+  float lb = l, r0 = 0.0f;
+  if (b != -INFINITY) {
+    const float hi = fmaxf(l, b);
+    lb = hi + log1pf(expf(-fabsf(l - b)));
+    r0 = expf(b - lb);
+  }
+  *lb_out = lb;
+  if (W) {
+    if (s == 0.0f) return INFINITY;
+    *n0 += s * r0;
+    *lik += s * lb;
+    return lb - ls;
+  }
+  *n0 += r0;
+  *lik += lb;
+  return lb;
+}
+
+template <bool W>
+__global__ void __launch_bounds__(NT)
+background_lse_kernel(const float* __restrict__ lse,
+                      const float* __restrict__ bg,
+                      const float* __restrict__ s,
+                      const float* __restrict__ lns,
+                      float* __restrict__ lse_m, float* __restrict__ lse_b,
+                      float* __restrict__ n0_part,
+                      float* __restrict__ lik_part, int64_t nvec,
+                      int64_t n) {
+  const float b = bg[1];
+  float n0 = 0.0f, lik = 0.0f;
+  const int64_t stride = (int64_t)gridDim.x * NT;
+  const int64_t t0 = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const f32x4* lse4 = reinterpret_cast<const f32x4*>(lse);
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(s);
+  const f32x4* lns4 = reinterpret_cast<const f32x4*>(lns);
+  f32x4* m4 = reinterpret_cast<f32x4*>(lse_m);
+  f32x4* b4 = reinterpret_cast<f32x4*>(lse_b);
+  for (int64_t v = t0; v < nvec; v += stride) {
+    const f32x4 l = lse4[v];
+    f32x4 sv = {1.0f, 1.0f, 1.0f, 1.0f}, ls = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (W) {
+      sv = s4[v];
+      ls = lns4[v];
+    }
+    f32x4 o, ob;
+#pragma unroll
+    for (int u = 0; u < EW_VEC; ++u) {
+      float lb;
+      o[u] = background_one<W>(l[u], b, sv[u], ls[u], &lb, &n0, &lik);
+      ob[u] = lb;
+    }
+    m4[v] = o;
+    if (lse_b != nullptr) b4[v] = ob;
+  }
+  for (int64_t e = nvec * EW_VEC + t0; e < n; e += stride) {
+    float lb;
+    lse_m[e] = background_one<W>(lse[e], b, W ? s[e] : 1.0f,
+                                 W ? lns[e] : 0.0f, &lb, &n0, &lik);
+    if (lse_b != nullptr) lse_b[e] = lb;
+  }
+  __shared__ float wsum0[NT / WAVE];
+  block_sum(n0, wsum0, n0_part);
+  if (lik_part != nullptr) {  // kernel argument: uniform over the block
+    __shared__ float wsum1[NT / WAVE];
+    block_sum(lik, wsum1, lik_part);
+  }
+}
+
+// One block: n0 = sum of the nparts background partials (the reduce_scalar
+// order: fixed per lane, then wave order), then the new background state
+//   bg[0] = pi0     = min(n0 / n_total, 1 - 1e-6)
+//   bg[1] = b       = ln pi0 - ln(1 - pi0) - lnV   (-inf at pi0 == 0)
+//   bg[2] = lik_add = n_total * ln(1 - pi0)
+//   bg[3] = n0
+// The scalar tail runs in double on one thread and rounds once per value.
+// No host synchronisation: the E-step that follows reads bg[1] on device.
+__global__ void __launch_bounds__(NT)
+background_update_kernel(const float* __restrict__ n0_part, int64_t nparts,
+                         double n_total, double ln_v,
+                         float* __restrict__ bg) {
+  float acc = 0.0f;
+  for (int64_t i = threadIdx.x; i < nparts; i += NT) acc += n0_part[i];
+  __shared__ float wsum[NT / WAVE];
+  for (int off = WAVE / 2; off > 0; off >>= 1)
+    acc += __shfl_down(acc, off, WAVE);
+  if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float n0 = 0.0f;
+    for (int wv = 0; wv < NT / WAVE; ++wv) n0 += wsum[wv];
+    double pi0 = (double)n0 / n_total;
+    if (!(pi0 > 0.0)) pi0 = 0.0;
+    if (pi0 > 1.0 - 1e-6) pi0 = 1.0 - 1e-6;
+    const double l1m = log1p(-pi0);
+    bg[0] = (float)pi0;
+    bg[1] = pi0 > 0.0 ? (float)(log(pi0) - l1m - ln_v) : -INFINITY;
+    bg[2] = (float)(n_total * l1m);
+    bg[3] = n0;
+  }
+}
+
 // Deterministic chunk reduction: out[j] = sum_i in[i*m + j] (fixed i
 // order). Replaces torch's generic reduce_kernel (19.6 us for the
 // [256, K*Pp] moments partials).

@@ -89,6 +89,18 @@ class GmmConfig:
     seed_method: str = "strided"
     seed_rng: int = 0
 
+    # Uniform background component for outliers: the mixture becomes
+    # (1 - pi0) * sum_c pi_c N_c(x) + pi0 / V with V the volume of the
+    # data's bounding box (background_log_volume = ln V; None: computed from
+    # the full data). It is switched on at pi0 = background_init after
+    # background_warmup plain EM iterations at the starting K: from the
+    # reference's R = I seeds the first quadratic forms are huge and a
+    # background present from the first E-step takes every event for good.
+    background: bool = False
+    background_init: float = 0.01
+    background_warmup: int = 5
+    background_log_volume: float | None = None
+
     def validate(self) -> None:
         if not (1 <= self.num_clusters <= MAX_CLUSTERS):
             raise ValueError(
@@ -117,6 +129,22 @@ class GmmConfig:
                 or not isinstance(self.seed_rng, int) or self.seed_rng < 0):
             raise ValueError(
                 f"seed_rng must be an integer >= 0: {self.seed_rng!r}")
+        if not (0.0 < float(self.background_init) < 1.0):
+            raise ValueError(
+                f"background_init must be in (0, 1): {self.background_init}")
+        if (isinstance(self.background_warmup, bool)
+                or not isinstance(self.background_warmup, int)
+                or self.background_warmup < 0):
+            raise ValueError("background_warmup must be an integer >= 0: "
+                             f"{self.background_warmup!r}")
+        if (self.background_log_volume is not None
+                and not math.isfinite(float(self.background_log_volume))):
+            raise ValueError("background_log_volume must be finite: "
+                             f"{self.background_log_volume}")
+        if self.background and self.checkpoint_dir:
+            raise ValueError(
+                "background cannot be combined with checkpoint_dir (the "
+                "checkpoint does not hold the background's state)")
 
     @property
     def stop_number(self) -> int:
@@ -136,15 +164,18 @@ def em_epsilon(num_dimensions: int, num_events: int) -> float:
 
 
 def rissanen_score(likelihood: float, num_clusters: int, num_dimensions: int,
-                   num_events: int) -> float:
+                   num_events: int, extra_params: int = 0) -> float:
     """Rissanen / MDL score (gaussian.cu:826).
 
-    rissanen = -L + 0.5*(K*(1 + D + 0.5*(D+1)*D) - 1)*ln(N*D)
+    rissanen = -L + 0.5*(K*(1 + D + 0.5*(D+1)*D) - 1 + extra)*ln(N*D)
+
+    ``extra_params`` counts free parameters beyond the Gaussians' (a
+    background component adds one, its weight).
     """
     d = num_dimensions
     params_per_cluster = 1 + d + 0.5 * (d + 1) * d
     return float(
         -likelihood
-        + 0.5 * (num_clusters * params_per_cluster - 1)
+        + 0.5 * (num_clusters * params_per_cluster - 1 + extra_params)
         * math.log(float(num_events) * d)
     )

@@ -122,36 +122,63 @@ def format_cluster_block(c: int, pi: float, n: float, means: np.ndarray,
     return "".join(parts)
 
 
-def write_summary(path: str, state, enable_output: bool = True) -> None:
+def write_summary(path: str, state, enable_output: bool = True,
+                  background: dict | None = None) -> None:
     """Writes <out>.summary (gaussian.cu:1015-1040).
 
     The file is always created; cluster blocks are written only when output
     is enabled, matching ENABLE_OUTPUT semantics.
+
+    ``background`` ({"pi", "n", "log_volume"}) is the uniform background of
+    a fit that has one: the cluster Probability lines then hold the mixture
+    weights (1 - pi0) * pi_c, and a trailing "Background" block its
+    Probability, N and Log volume as %f.
     """
+    scale = 1.0 - float(background["pi"]) if background else 1.0
     with open(path, "w") as f:
         if enable_output:
             for c in range(state.num_clusters):
                 f.write(f"Cluster #{c}\n")
                 f.write(
                     format_cluster_block(
-                        c, float(state.pi[c]), float(state.N[c]),
+                        c, scale * float(state.pi[c]), float(state.N[c]),
                         np.asarray(state.means[c]), np.asarray(state.R[c]),
                     )
                 )
                 f.write("\n\n")
+            if background:
+                f.write("Background\n"
+                        f"Probability: {float(background['pi']):f}\n"
+                        f"N: {float(background['n']):f}\n"
+                        f"Log volume: {float(background['log_volume']):f}\n"
+                        "\n\n")
 
 
 def read_summary(path: str) -> dict[str, np.ndarray]:
     """Parses a .summary file in the layout format_cluster_block writes
     (this project's or the reference's): pi [K], N [K], means [K, D] and
     R [K, D, D] as float32. The file holds %.3f / %f text, so the values
-    are rounded to that. Raises ValueError on anything else."""
+    are rounded to that. A trailing "Background" block (write_summary)
+    adds background_pi, background_n and background_log_volume as float64
+    scalars; the pi of such a file are mixture weights (1 - pi0) * pi_c.
+    Raises ValueError on anything else."""
     with open(path, "r") as f:
         lines = [ln.strip() for ln in f]
     pi, n, means, rs = [], [], [], []
+    background = {}
     i = 0
     try:
         while i < len(lines):
+            if lines[i] == "Background" and not background:
+                background = {
+                    "background_pi": np.float64(
+                        lines[i + 1].split("Probability:")[1]),
+                    "background_n": np.float64(lines[i + 2].split("N:")[1]),
+                    "background_log_volume": np.float64(
+                        lines[i + 3].split("Log volume:")[1]),
+                }
+                i += 4
+                continue
             if not lines[i].startswith("Cluster #"):
                 if lines[i]:
                     raise ValueError(f"unexpected line {i + 1}: {lines[i]!r}")
@@ -181,6 +208,7 @@ def read_summary(path: str) -> dict[str, np.ndarray]:
         "N": np.asarray(n, dtype=np.float32),
         "means": np.asarray(means, dtype=np.float32),
         "R": np.asarray(rs, dtype=np.float32),
+        **background,
     }
 
 
