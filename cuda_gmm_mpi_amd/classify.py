@@ -5,6 +5,8 @@ MODEL is a .npz written by ``gmm ... --save-model`` or, chosen by its
 suffix, a .summary file (lossy: %.3f parameters). Writes OUTSTEM.labels,
 one line per event: ``label,max posterior,log-probability`` as %d,%f,%f.
 A model with a uniform background labels the events it assigns to it -1.
+A model with Student-t components (``gmm --student-t NU``) is scored with
+its t densities.
 
 Exit codes: 0 ok, 1 bad arguments, 2 unreadable INFILE (as ``gmm``),
 5 unreadable MODEL or a model / data dimension mismatch.
@@ -107,6 +109,7 @@ def main(argv=None) -> int:
                 "log_likelihood": pred.log_likelihood,
                 "counts": pred.counts.tolist(),
                 "background_count": pred.background_count,
+                "student_t_nu": model.student_t_nu,
                 "device": device,
                 "seconds": elapsed,
             }, f, indent=2)

@@ -99,6 +99,14 @@ def make_parser() -> argparse.ArgumentParser:
                    metavar="X",
                    help="ln of the background's volume (default: the "
                         "bounding box of the data)")
+    p.add_argument("--student-t", type=float, default=0.0, metavar="NU",
+                   dest="student_t",
+                   help="Student-t mixture components with NU degrees of "
+                        "freedom (fixed; flowClust uses 4): events in a "
+                        "population's tail are down-weighted instead of "
+                        "inflating its covariance. The R matrices are then "
+                        "scale matrices (covariance NU / (NU - 2) * R). Not "
+                        "with --background or --checkpoint-dir")
     p.add_argument("--gpus", type=int, default=None,
                    help="spawn N single-GPU worker processes on this node "
                         "(one rank per GPU over RCCL)")
@@ -133,6 +141,7 @@ def config_from_args(args) -> GmmConfig:
         background=args.background, background_init=args.background_init,
         background_warmup=args.background_warmup,
         background_log_volume=args.background_log_volume,
+        student_t_nu=args.student_t,
     )
     cfg.validate()
     return cfg
@@ -203,7 +212,8 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                                 cfg.diag_only, cfg.bug_compat,
                                 background_pi=result.background_pi,
                                 background_log_volume=(
-                                    result.background_log_volume))
+                                    result.background_log_volume),
+                                student_t_nu=cfg.student_t_nu)
     if save_model and rank == 0:
         model.save(save_model)
     memberships = None
@@ -220,12 +230,14 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
                               w_shard.cpu().numpy())
         if rank == 0:
             gio.write_summary(outfile + ".summary", out_state,
-                              cfg.enable_output, background)
+                              cfg.enable_output, background,
+                              cfg.student_t_nu)
     else:
         memberships = engine.gather_memberships(w_shard)
         if rank == 0:
             gio.write_summary(outfile + ".summary", out_state,
-                              cfg.enable_output, background)
+                              cfg.enable_output, background,
+                              cfg.student_t_nu)
             if cfg.enable_output and write_results and memberships is not None:
                 gio.write_results(outfile + ".results", data, memberships)
 
@@ -254,6 +266,7 @@ def run_clustering(data: np.ndarray | None, cfg: GmmConfig, outfile: str,
         "background_n": result.background_n if cfg.background else None,
         "background_log_volume": (result.background_log_volume
                                   if cfg.background else None),
+        "student_t_nu": float(cfg.student_t_nu),
     }
 
 
@@ -394,6 +407,7 @@ def main(argv=None) -> int:
                     "background_n": result["background_n"],
                     "background_log_volume":
                         result["background_log_volume"],
+                    "student_t_nu": result["student_t_nu"],
                 }, f, indent=2)
         if rank == 0 and args.enable_print:
             print(f"Ideal clusters: {result['num_clusters']} "

@@ -141,10 +141,14 @@ class EmEngine:
                     "data: build the engine with build_engine or set "
                     "background_log_volume")
             self.bg_log_volume = float(lnv)
-        if self.s is not None or self.background:
-            # the weights and the background ride on the lse the M-step
-            # kernels subtract; the LDS variant writes posteriors and has
-            # no lse. The lse family handles any K.
+        # Student-t components with fixed degrees of freedom (0: Gaussian,
+        # and nothing below is allocated or dispatched differently)
+        self.nu = float(config.student_t_nu)
+        self.student_t = self.nu > 0.0
+        if self.s is not None or self.background or self.student_t:
+            # the weights, the background and the t pass ride on the lse
+            # the M-step kernels subtract; the LDS variant writes posteriors
+            # and has no lse. The lse family handles any K.
             self.use_lds_estep = False
         self.use_big_estep = F.estep_big_available(
             self.device, config.estep_dtype, self.d,
@@ -220,6 +224,23 @@ class EmEngine:
                     self._lse_b = torch.empty_like(self._lse)
             else:
                 self._lse_b = torch.empty(self.n_shard, dtype=torch.float32)
+        # Student-t: the responsibilities n_c = sum_e s_e tau_ce of the last
+        # E-step (N and pi come from them; the moments' corner holds
+        # sum s tau u), and on CUDA the t lse plus the kernel's block
+        # partials. _lse_w is the lse the moments read, as for the weights.
+        self._t_n: torch.Tensor | None = None
+        self._lse_t: torch.Tensor | None = None
+        self._t_npart: torch.Tensor | None = None
+        self._t_likpart: torch.Tensor | None = None
+        if self.student_t:
+            self._t_n = torch.zeros(k0, dtype=torch.float32,
+                                    device=self.device)
+            if self.device.type == "cuda":
+                self._lse_t = torch.empty_like(self._lse)
+                if self._lse_w is None:
+                    self._lse_w = torch.empty_like(self._lse)
+                self._t_npart, self._t_likpart = F.student_t_partials(
+                    self.n_shard, k0, self.device)
         self.epsilon = em_epsilon(self.d, self.n_total)
         self.likelihood = 0.0
         # hipGraph capture of the EM iteration (launch-overhead elimination);
@@ -318,9 +339,10 @@ class EmEngine:
         st = self.state.shrink(k)
         weighted = self.s is not None
         want_lik = need_lik
-        if (weighted or self.background) and self.device.type == "cuda":
-            # the event-weight / background kernel below produces the
-            # likelihood
+        if ((weighted or self.background or self.student_t)
+                and self.device.type == "cuda"):
+            # the event-weight / background / Student-t kernel below
+            # produces the likelihood
             need_lik = False
         with self.profile.time("e_step"):
             self._w_is_logw = False
@@ -357,23 +379,36 @@ class EmEngine:
                 else:
                     logw = F.estep_logw_big(self.x_estep, self.mfac[:k],
                                             add, self.w[:k])
-                lik = F.estep_lse(logw, self._lse, need_lik,
-                                  lik_out=self._lik_dev)
+                # (a t fit takes its lse from the t pass below)
+                lik = (None if self.student_t else
+                       F.estep_lse(logw, self._lse, need_lik,
+                                   lik_out=self._lik_dev))
                 self._w_is_logw = True
             elif self.device.type == "cuda":
                 logw = F.estep_logw(
                     self.x_estep, st.means, st.Rinv, st.constant, st.pi,
                     self.cfg.diag_only, out=self.w[:k],
                 )
-                lik = F.estep_lse(logw, self._lse, need_lik,
-                                  lik_out=self._lik_dev)
+                lik = (None if self.student_t else
+                       F.estep_lse(logw, self._lse, need_lik,
+                                   lik_out=self._lik_dev))
                 self._w_is_logw = True
+                if self.student_t:
+                    # the offsets this kernel added, to within an ulp (its
+                    # constant + ln pi in the same order; the recovered q
+                    # moves by that ulp and is clamped at 0)
+                    add = F.logw_offsets(st.constant, st.pi)
             else:
                 logw = F.estep_logw(
                     self.x_estep, st.means, st.Rinv, st.constant, st.pi,
                     self.cfg.diag_only, out=self.w[:k],
                 )
-                if self.background:
+                if self.student_t:
+                    # w = tau, the t posteriors; the M-step reads s tau u
+                    w, self._w_s, lik = F.estep_posteriors_student_t(
+                        logw, F.logw_offsets(st.constant, st.pi), self.nu,
+                        self.d, self.s, self._t_n[:k])
+                elif self.background:
                     # w = exp(logw - lse_b): columns sum to 1 - r0; the
                     # M-step reads it, times s in a weighted fit
                     w, self._w_s, lik = F.estep_posteriors_background(
@@ -385,13 +420,22 @@ class EmEngine:
                         logw, self.s)
                 else:
                     w, lik = F.estep_posteriors(logw)
-            if (weighted or self.background) and self.device.type == "cuda":
+            if ((weighted or self.background or self.student_t)
+                    and self.device.type == "cuda"):
                 if not self._w_is_logw:
                     raise RuntimeError(
-                        "per-event weights and the background need an "
-                        "E-step of the lse family (use_lds_estep must stay "
-                        "off)")
-                if self.background:
+                        "per-event weights, the background and Student-t "
+                        "components need an E-step of the lse family "
+                        "(use_lds_estep must stay off)")
+                if self.student_t:
+                    # rewrites the log weights to ln(s tau u) + lse_m; with
+                    # weights it replaces event_weight_lse
+                    lik = F.student_t_lse(
+                        self.w[:k], add, self.nu, self.d, self.s, self._lns,
+                        self._lse_w, self._lse_t, self._t_npart,
+                        self._t_likpart, self._t_n[:k], want_lik,
+                        lik_out=self._lik_dev)
+                elif self.background:
                     lik = self._background_lse(want_lik)
                 else:
                     lik = F.event_weight_lse(self._lse, self.s, self._lns,
@@ -543,6 +587,8 @@ class EmEngine:
                 )
             self.profile.count("params")
             self.profile.count("constants")
+            if self.student_t:
+                self._student_t_pi(k)
             return
         with self.profile.time("m_step"):
             if self.device.type == "cuda":
@@ -565,6 +611,25 @@ class EmEngine:
         self._update_constants(st)
         if self.device.type != "cuda":
             st.pi.copy_(F.compute_pi(st.N))
+        if self.student_t:
+            self._student_t_pi(k)
+
+    def _student_t_pi(self, k: int) -> None:
+        """After finalize and the constants: N and pi (and the E-step's add
+        buffer) of a t fit from the responsibilities of the last E-step,
+        all-reduced over the world first (K floats). Finalize's own N and pi
+        come from the moments' corner, which holds sum s tau u."""
+        st = self.state.shrink(k)
+        n_c = self._t_n[:k]
+        if self.world > 1:
+            # into a scratch K-vector: _t_n keeps the shard's own sums, so
+            # an M-step repeated without an E-step reduces them again, not
+            # the already reduced values
+            n_c = n_c.clone()
+            with self.profile.time("comm"):
+                pdist.all_reduce_(n_c)
+        F.student_t_pi(n_c, st.constant, st.N, st.pi,
+                       self._add[:k] if self._add is not None else None)
 
     def run_em(self, k: int) -> float:
         """Full EM at fixed K (the inner loop of gaussian.cu:479-755).
@@ -906,7 +971,15 @@ class EmEngine:
 
     def posteriors(self, k: int) -> torch.Tensor:
         """Normalized posteriors [k, n_shard] for the current E-step state
-        (paths that emit log weights normalize with the lse)."""
+        (paths that emit log weights normalize with the lse).
+
+        A Student-t fit on CUDA is the exception: its buffer holds
+        ln(s tau u) + lse_m, from which tau cannot be read back, so the t
+        posteriors are recomputed from the CURRENT parameters by a fresh
+        E-step into a second [k, n_shard] buffer (as recompute_memberships
+        does). Called straight after an E-step that is the last E-step's
+        tau; called after an M-step it is the tau of the new parameters,
+        not what the buffers hold."""
         if self.background:
             # K + 1 rows, the background's posterior last
             b = self._bg[1]
@@ -916,6 +989,13 @@ class EmEngine:
             if getattr(self, "_w_is_logw", False):
                 w = torch.exp(w - self._lse_b.unsqueeze(0))
             return torch.cat([w, r0.unsqueeze(0)], dim=0)
+        if self.student_t:
+            # tau, never tau * u. The CUDA buffer holds ln(tau u) + lse_t:
+            # regenerate from the parameters the last E-step used
+            if self.device.type != "cuda":
+                return self.w[:k]
+            self._refresh_rinv(k)
+            return self.recompute_memberships(self.state.shrink(k))
         if self._lse is None or not getattr(self, "_w_is_logw", False):
             return self.w[:k]
         return torch.exp(self.w[:k] - self._lse.unsqueeze(0))
@@ -944,6 +1024,10 @@ class EmEngine:
             pi0 = (self.background_pi if background_pi is None
                    else float(background_pi))
             return F.background_posteriors(logw, pi0, self.bg_log_volume)
+        if self.student_t:
+            w, _ = F.student_t_posteriors(
+                logw, F.logw_offsets(st.constant, st.pi), self.nu, self.d)
+            return w
         w, _ = F.estep_posteriors(logw)
         return w
 

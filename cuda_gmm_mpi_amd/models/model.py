@@ -31,8 +31,12 @@ _ARRAYS = ("center", "means_centered", "pi", "N", "constant", "avgvar",
 _FLAGS = ("diag_only", "bug_compat")
 _KEYS = ("format_version",) + _ARRAYS + _FLAGS
 _BACKGROUND = ("background_pi", "background_log_volume")
+# a model with Student-t components: version 1 plus the degrees of freedom
+FORMAT_VERSION_STUDENT_T = 3
+_STUDENT_T = ("student_t_nu",)
 _KEYS_BY_VERSION = {FORMAT_VERSION: _KEYS,
-                    FORMAT_VERSION_BACKGROUND: _KEYS + _BACKGROUND}
+                    FORMAT_VERSION_BACKGROUND: _KEYS + _BACKGROUND,
+                    FORMAT_VERSION_STUDENT_T: _KEYS + _STUDENT_T}
 
 
 @dataclasses.dataclass
@@ -76,6 +80,10 @@ class GmmModel:
     # normalised among the clusters. background_pi == 0: no background.
     background_pi: float = 0.0
     background_log_volume: float = 0.0
+    # Student-t components with this many degrees of freedom (0: Gaussian).
+    # R is then the scale matrix and `constant` stays the Gaussian one: the
+    # t normaliser adds the same delta(nu, D) to every cluster.
+    student_t_nu: float = 0.0
 
     def __post_init__(self):
         for name in _ARRAYS:
@@ -85,6 +93,7 @@ class GmmModel:
         self.bug_compat = bool(self.bug_compat)
         self.background_pi = float(self.background_pi)
         self.background_log_volume = float(self.background_log_volume)
+        self.student_t_nu = float(self.student_t_nu)
         self._validate()
 
     def _validate(self) -> None:
@@ -101,6 +110,14 @@ class GmmModel:
                 f"inconsistent model: background_pi {self.background_pi} "
                 f"must be in [0, 1) and background_log_volume "
                 f"{self.background_log_volume} finite")
+        if not (np.isfinite(self.student_t_nu) and self.student_t_nu >= 0.0):
+            raise ValueError(
+                f"inconsistent model: student_t_nu {self.student_t_nu} must "
+                f"be finite and >= 0")
+        if self.student_t_nu > 0.0 and self.background_pi > 0.0:
+            raise ValueError(
+                "inconsistent model: Student-t components cannot be combined "
+                "with a background")
         for name, shape in want.items():
             got = tuple(getattr(self, name).shape)
             if got != shape:
@@ -121,6 +138,10 @@ class GmmModel:
         return self.background_pi > 0.0
 
     @property
+    def is_student_t(self) -> bool:
+        return self.student_t_nu > 0.0
+
+    @property
     def means(self) -> torch.Tensor:
         """Cluster means in the data's own frame."""
         return self.means_centered + self.center.unsqueeze(0)
@@ -131,7 +152,8 @@ class GmmModel:
     def from_state(cls, state: GmmState, center: torch.Tensor,
                    diag_only: bool = False,
                    bug_compat: bool = True, background_pi: float = 0.0,
-                   background_log_volume: float = 0.0) -> "GmmModel":
+                   background_log_volume: float = 0.0,
+                   student_t_nu: float = 0.0) -> "GmmModel":
         """From an engine state whose means are in the centred frame."""
         return cls(center=center.clone(), means_centered=state.means.clone(),
                    pi=state.pi.clone(), N=state.N.clone(),
@@ -140,13 +162,16 @@ class GmmModel:
                    Rinv=state.Rinv.clone(), diag_only=diag_only,
                    bug_compat=bug_compat, background_pi=background_pi,
                    background_log_volume=(background_log_volume
-                                          if background_pi > 0.0 else 0.0))
+                                          if background_pi > 0.0 else 0.0),
+                   student_t_nu=student_t_nu)
 
     @classmethod
     def from_params(cls, means, R, pi, N=None, center=None,
                     diag_only: bool = False, background_pi: float = 0.0,
-                    background_log_volume: float = 0.0) -> "GmmModel":
-        """From means [K, D] (data frame), covariances and weights; Rinv and
+                    background_log_volume: float = 0.0,
+                    student_t_nu: float = 0.0) -> "GmmModel":
+        """From means [K, D] (data frame), covariances (scale matrices for a
+        t model, ``student_t_nu`` > 0) and weights; Rinv and
         constant come from cpu_reference.compute_constants (natural log).
         The default centre is the pi-weighted mean of the means."""
         means = torch.as_tensor(means, dtype=torch.float32)
@@ -164,7 +189,8 @@ class GmmModel:
                    constant=constant, avgvar=torch.zeros(k), R=r, Rinv=rinv,
                    diag_only=diag_only, bug_compat=False,
                    background_pi=background_pi,
-                   background_log_volume=background_log_volume)
+                   background_log_volume=background_log_volume,
+                   student_t_nu=student_t_nu)
 
     @classmethod
     def from_summary(cls, path: str) -> "GmmModel":
@@ -178,7 +204,9 @@ class GmmModel:
         s = read_summary(path)
         pi0 = float(s.get("background_pi", 0.0))
         if pi0 <= 0.0:
-            return cls.from_params(s["means"], s["R"], s["pi"], N=s["N"])
+            return cls.from_params(
+                s["means"], s["R"], s["pi"], N=s["N"],
+                student_t_nu=float(s.get("student_t_nu", 0.0)))
         # the cluster lines hold (1 - pi0) * pi_c: back to pi_c, normalised
         # among the clusters
         pi = s["pi"].astype(np.float64) / (1.0 - pi0)
@@ -190,10 +218,12 @@ class GmmModel:
     # ------------------------------------------------------------- save/load
 
     def save(self, path: str) -> None:
-        """One .npz, every field fp32, written atomically. A model without
-        a background writes format version 1, one with it version 2 (the
-        two background scalars added, as float64)."""
+        """One .npz, every field fp32, written atomically. A plain Gaussian
+        model writes format version 1, one with a background version 2 (the
+        two background scalars added, as float64), one with Student-t
+        components version 3 (version 1 plus student_t_nu, as float64)."""
         version = (FORMAT_VERSION_BACKGROUND if self.has_background
+                   else FORMAT_VERSION_STUDENT_T if self.is_student_t
                    else FORMAT_VERSION)
         payload = {"format_version": np.float32(version)}
         for name in _ARRAYS:
@@ -202,6 +232,10 @@ class GmmModel:
             payload[name] = np.float32(getattr(self, name))
         if self.has_background:
             for name in _BACKGROUND:
+                payload[name] = np.float64(getattr(self, name))
+        if self.is_student_t:
+            # version 3: version 1 plus the degrees of freedom (float64)
+            for name in _STUDENT_T:
                 payload[name] = np.float64(getattr(self, name))
         # np.savez appends .npz when missing — keep the suffix on the temp name
         tmp = f"{path}.tmp.{os.getpid()}.npz"
@@ -239,14 +273,14 @@ class GmmModel:
             raise ValueError(f"cannot load model {path}: format version "
                              f"{version:g}, this build reads "
                              f"{sorted(_KEYS_BY_VERSION)}")
-        background = {name: float(fields[name]) for name in _BACKGROUND
-                      if name in fields}
+        scalars = {name: float(fields[name])
+                   for name in _BACKGROUND + _STUDENT_T if name in fields}
         try:
             return cls(**{name: torch.from_numpy(
                               fields[name].astype(np.float32))
                           for name in _ARRAYS},
                        diag_only=bool(fields["diag_only"]),
-                       bug_compat=bool(fields["bug_compat"]), **background)
+                       bug_compat=bool(fields["bug_compat"]), **scalars)
         except ValueError as e:
             raise ValueError(f"cannot load model {path}: {e}") from None
 
@@ -302,7 +336,9 @@ class GmmModel:
         max_post = np.empty(n, dtype=np.float32)
         st = self._on(dev)
         center = self.center.to(dev)
-        fused = F.estep_classify_available(dev, d)
+        # a t model takes the [K, n]-buffer route at every D (the fused
+        # classify kernel is Gaussian-only)
+        fused = F.estep_classify_available(dev, d) and not self.is_student_t
         big = (not fused) and F.estep_big_available(dev, estep_dtype, d)
         if fused or big:  # factor tables: once per call
             fac, add = F.model_factor_tables(
@@ -324,15 +360,34 @@ class GmmModel:
                 else:
                     logw = F.estep_logw(z, st.means, st.Rinv, st.constant,
                                         st.pi, self.diag_only)
-                lse = torch.empty(e - s, dtype=torch.float32, device=dev)
-                F.estep_lse(logw, lse, need_lik=False)
+                if self.is_student_t:
+                    # log-weights -> student_t_lse(posterior) -> argmax
+                    logw, lse = F.student_t_posteriors(
+                        logw, add if big else F.logw_offsets(st.constant,
+                                                             st.pi),
+                        self.student_t_nu, d)
+                else:
+                    lse = torch.empty(e - s, dtype=torch.float32, device=dev)
+                    F.estep_lse(logw, lse, need_lik=False)
                 m = logw.max(dim=0).values
                 idx = torch.arange(k, dtype=torch.int32,
                                    device=dev).unsqueeze(1)
                 lab = torch.where(logw == m.unsqueeze(0), idx,
                                   torch.full_like(idx, k)
                                   ).min(dim=0).values.clamp(max=k - 1)
-                pmax = torch.exp(m - lse)
+                pmax = m if self.is_student_t else torch.exp(m - lse)
+            elif self.is_student_t:
+                logw = cpu.estep_logw(
+                    self._stage(chunk, center, estep_dtype), st.means,
+                    st.Rinv, st.constant, st.pi, self.diag_only)
+                _, lse, tau = cpu.student_t_posteriors(
+                    logw, F.logw_offsets(st.constant, st.pi),
+                    self.student_t_nu, d)
+                pmax = tau.max(dim=0).values
+                idx = torch.arange(k, dtype=torch.int32).unsqueeze(1)
+                lab = torch.where(tau == pmax.unsqueeze(0), idx,
+                                  torch.full_like(idx, k)
+                                  ).min(dim=0).values.clamp(max=k - 1)
             else:
                 lab, lse, pmax = cpu.classify(
                     self._stage(chunk, center, estep_dtype), st.means,
@@ -395,7 +450,11 @@ class GmmModel:
             z = self._stage(x[s:e].to(dev), center, estep_dtype)
             logw = F.estep_logw(z, st.means, st.Rinv, st.constant, st.pi,
                                 self.diag_only)
-            if self.has_background:
+            if self.is_student_t:
+                w, _ = F.student_t_posteriors(
+                    logw, F.logw_offsets(st.constant, st.pi),
+                    self.student_t_nu, self.num_dimensions)
+            elif self.has_background:
                 w = F.background_posteriors(logw, self.background_pi,
                                             self.background_log_volume)
             else:

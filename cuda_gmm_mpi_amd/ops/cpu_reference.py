@@ -158,6 +158,120 @@ def estep_posteriors_background(logw: torch.Tensor, b: float,
     return w, w_s, lse_b, n0, lik
 
 
+def student_t_delta(nu: float, d: int) -> float:
+    """delta(nu, D) = lgamma((nu + D) / 2) - lgamma(nu / 2) - D/2 ln(nu / 2):
+    what the t normaliser adds to the Gaussian ``constant`` (float64; the
+    same for every cluster). It tends to 0 as nu grows."""
+    nu = float(nu)
+    return (math.lgamma(0.5 * (nu + d)) - math.lgamma(0.5 * nu)
+            - 0.5 * d * math.log(0.5 * nu))
+
+
+def student_t_lse(logw: torch.Tensor, add: torch.Tensor, nu: float, d: int,
+                  s: torch.Tensor | None = None, train: bool = True
+                  ) -> tuple[torch.Tensor, torch.Tensor,
+                             torch.Tensor | None, torch.Tensor | None,
+                             torch.Tensor | None]:
+    """CPU twin of the Student-t kernel, fp32: Gaussian log-weights
+    logw [K, N] = add_c - q/2 become t ones.
+
+    q = max(0, 2 (add_c - logw)); lt = add_c + delta - (nu + D)/2 log1p(q/nu);
+    lse_t = logsumexp_c lt (-inf where every lt is); u = (nu + D)/(nu + q).
+    Returns (logw_out, lse_t, lse_m, n_c, lik). ``train``: logw_out =
+    lt + ln u, lse_m = lse_t or event_weight_lse of it with weights s,
+    n_c [K] = sum_e s_e exp(lt - lse_t) and lik = sum_e s_e lse_t, zero-weight
+    events skipped and events with lse_t = -inf adding exact zeros to n_c.
+    Posterior mode: logw_out = lt and the last three are None."""
+    lt, lnu, lse_t, dead = _student_t_terms(logw, add, nu, d)
+    if not train:
+        return lt, lse_t, None, None, None
+    out = lt + lnu
+    tau = _student_t_tau(lt, lse_t, dead)
+    if s is None:
+        return out, lse_t, lse_t, tau.sum(dim=1), lse_t.sum()
+    lse_m, lik = event_weight_lse(lse_t, s, torch.log(s))
+    n_c = torch.where((s == 0).unsqueeze(0), torch.zeros_like(tau),
+                      tau * s.unsqueeze(0)).sum(dim=1)
+    return out, lse_t, lse_m, n_c, lik
+
+
+def _student_t_terms(logw: torch.Tensor, add: torch.Tensor, nu: float,
+                     d: int) -> tuple[torch.Tensor, torch.Tensor,
+                                      torch.Tensor, torch.Tensor]:
+    """(lt [K, N], ln u [K, N], lse_t [N], dead [N]: every lt is -inf)."""
+    nu32 = torch.tensor(float(nu), dtype=torch.float32)
+    nud = torch.tensor(float(nu) + float(d), dtype=torch.float32)
+    delta = torch.tensor(student_t_delta(nu, d), dtype=torch.float32)
+    a = add.unsqueeze(1)
+    q = (2.0 * (a - logw)).clamp(min=0.0)
+    lt = (a + delta) - (0.5 * nud) * torch.log1p(q / nu32)
+    m = lt.max(dim=0).values
+    dead = m == float("-inf")
+    m_safe = torch.where(dead, torch.zeros_like(m), m)
+    lse_t = torch.where(
+        dead, m, m_safe + torch.log(torch.exp(lt - m_safe.unsqueeze(0))
+                                    .sum(dim=0)))
+    return lt, torch.log(nud / (nu32 + q)), lse_t, dead
+
+
+def _student_t_tau(lt: torch.Tensor, lse_t: torch.Tensor,
+                   dead: torch.Tensor) -> torch.Tensor:
+    """exp(lt - lse_t), exact zeros for the events whose lt are all -inf."""
+    safe = torch.where(dead, torch.zeros_like(lse_t), lse_t)
+    return torch.where(dead.unsqueeze(0), torch.zeros_like(lt),
+                       torch.exp(lt - safe.unsqueeze(0)))
+
+
+def student_t_pi(n_c: torch.Tensor, constant: torch.Tensor | None = None
+                 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None]:
+    """CPU twin of the one-block kernel after finalize: (N, pi, add) of a t
+    fit from the reduced responsibilities n_c [K] = sum_e s_e tau_ce.
+    pi = n_c / sum n_c (summed in cluster order in fp32), 1e-10 where
+    n_c < 0.5; add = constant + ln pi when ``constant`` is given."""
+    total = torch.zeros((), dtype=torch.float32)
+    for c in range(int(n_c.numel())):
+        total = total + n_c[c]
+    pi = torch.where(n_c < 0.5, torch.full_like(n_c, 1e-10), n_c / total)
+    add = None if constant is None else constant + torch.log(pi)
+    return n_c.clone(), pi, add
+
+
+def estep_posteriors_student_t(logw: torch.Tensor, add: torch.Tensor,
+                               nu: float, d: int,
+                               s: torch.Tensor | None = None
+                               ) -> tuple[torch.Tensor, torch.Tensor,
+                                          torch.Tensor, torch.Tensor]:
+    """E-step of a t fit on the CPU engine: (tau [K, N], the t posteriors;
+    w_m = s tau u, what the parameter-expanded M-step sums; n_c [K];
+    lik)."""
+    lt, lnu, lse_t, dead = _student_t_terms(logw, add, nu, d)
+    # the kernel's arithmetic: tau = exp(lt - lse_t) for output, and the
+    # M-step weight exp((lt + ln u) - lse_m) with lse_m = lse_t - ln s
+    tau = torch.exp(lt - lse_t.unsqueeze(0))
+    tau_n = _student_t_tau(lt, lse_t, dead)
+    if s is None:
+        lse_m, lik, n_c = lse_t, lse_t.sum(), tau_n.sum(dim=1)
+    else:
+        lse_m, lik = event_weight_lse(lse_t, s, torch.log(s))
+        n_c = torch.where((s == 0).unsqueeze(0), torch.zeros_like(tau_n),
+                          tau_n * s.unsqueeze(0)).sum(dim=1)
+    w_m = torch.exp((lt + lnu) - lse_m.unsqueeze(0))
+    # exact zeros only where the contract has them: events with s == 0 and
+    # events whose lt are all -inf; any other NaN stays visible
+    zero = dead if s is None else dead | (s == 0)
+    w_m = torch.where(zero.unsqueeze(0), torch.zeros_like(w_m), w_m)
+    return tau, w_m, n_c, lik
+
+
+def student_t_posteriors(logw: torch.Tensor, add: torch.Tensor, nu: float,
+                         d: int) -> tuple[torch.Tensor, torch.Tensor,
+                                          torch.Tensor]:
+    """(lt [K, N], lse_t [N], tau [K, N] = exp(lt - lse_t)) from Gaussian
+    log-weights: the output and scoring path (posterior mode)."""
+    lt, lse_t, _, _, _ = student_t_lse(logw, add, nu, d, None, False)
+    return lt, lse_t, torch.exp(lt - lse_t.unsqueeze(0))
+
+
 def classify(x: torch.Tensor, means: torch.Tensor, rinv: torch.Tensor,
              constant: torch.Tensor, pi: torch.Tensor,
              diag_only: bool = False

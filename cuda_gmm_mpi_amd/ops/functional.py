@@ -227,6 +227,103 @@ def background_posteriors(logw: torch.Tensor, pi0: float,
                       r0.unsqueeze(0)], dim=0)
 
 
+student_t_delta = cpu.student_t_delta
+
+
+def student_t_partials(n: int, k: int, device
+                       ) -> tuple[torch.Tensor, torch.Tensor]:
+    """(n_part [blocks, K], lik_part [blocks]) for student_t_lse over n
+    events on ``device`` (CUDA). Every launched block writes its row and its
+    slot, so they are never zero-filled."""
+    blocks = int(hip_ext().student_t_lse_blocks(n))
+    return (torch.empty((blocks, k), dtype=torch.float32, device=device),
+            torch.empty(blocks, dtype=torch.float32, device=device))
+
+
+def student_t_lse(logw: torch.Tensor, add: torch.Tensor, nu: float, d: int,
+                  s: torch.Tensor | None, lns: torch.Tensor | None,
+                  lse_m: torch.Tensor, lse_t: torch.Tensor,
+                  n_part: torch.Tensor, lik_part: torch.Tensor,
+                  n_c: torch.Tensor, need_lik: bool = True,
+                  lik_out: torch.Tensor | None = None
+                  ) -> torch.Tensor | None:
+    """Student-t components on the lse family, train mode (CUDA). ``logw``
+    [K, N] holds the Gaussian log-weights add_c - q/2 of any lse-family
+    E-step and is rewritten in place to lt + ln u; writes lse_m [N] (what the
+    lse-aware M-step kernels read: lse_t, with weights lse_t - lns and +inf
+    at s == 0 — it replaces event_weight_lse), lse_t [N], and reduces the
+    block partials of the responsibilities into n_c [K]. With ``need_lik``
+    returns sum_e s_e lse_t reduced into ``lik_out`` [1] when given.
+    Contract: cpu_reference.student_t_lse."""
+    ext = hip_ext()
+    empty = logw.new_empty(0)
+    k = logw.shape[0]
+    # a sweep shrinks K: the first blocks * K floats of the buffer, as rows
+    part = n_part.reshape(-1)[:lik_part.numel() * k].view(-1, k)
+    ext.student_t_lse(logw, add, s if s is not None else empty,
+                      lns if s is not None else empty, lse_m, lse_t,
+                      part, lik_part if need_lik else empty,
+                      float(nu), int(d), student_t_delta(nu, d), True)
+    ext.reduce_chunks(part, n_c)
+    if not need_lik:
+        return None
+    lik = (lik_out if lik_out is not None
+           else torch.empty(1, dtype=torch.float32, device=logw.device))
+    ext.reduce_scalar(lik_part, lik)
+    return lik
+
+
+def student_t_posteriors(logw: torch.Tensor, add: torch.Tensor, nu: float,
+                         d: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(tau [K, N], lse_t [N]): the t posteriors and ln p(x_e) from Gaussian
+    log-weights logw = add_c - q/2, which is overwritten (posterior mode of
+    the kernel, then exp(lt - lse_t) in place). The output / scoring path."""
+    if not logw.is_cuda:
+        _, lse_t, tau = cpu.student_t_posteriors(logw, add, nu, d)
+        logw.copy_(tau)
+        return logw, lse_t
+    lse_t = torch.empty(logw.shape[1], dtype=torch.float32,
+                        device=logw.device)
+    empty = logw.new_empty(0)
+    hip_ext().student_t_lse(logw, add.contiguous(), empty, empty, empty,
+                            lse_t, empty, empty, float(nu), int(d),
+                            student_t_delta(nu, d), False)
+    logw.sub_(lse_t.unsqueeze(0)).exp_()
+    return logw, lse_t
+
+
+def student_t_pi(n_c: torch.Tensor, constant: torch.Tensor | None,
+                 n_out: torch.Tensor, pi: torch.Tensor,
+                 add: torch.Tensor | None = None) -> None:
+    """N <- n_c, pi <- n_c / sum n_c (1e-10 where n_c < 0.5) and, when
+    ``add`` is given, add <- constant + ln pi: the mixing weights of a t fit
+    come from the responsibilities, not from the moments' corner. One block
+    on CUDA, no host sync. Contract: cpu_reference.student_t_pi."""
+    if not n_c.is_cuda:
+        n, p, a = cpu.student_t_pi(n_c, constant if add is not None else None)
+        n_out.copy_(n)
+        pi.copy_(p)
+        if add is not None:
+            add.copy_(a)
+        return
+    empty = n_c.new_empty(0)
+    hip_ext().student_t_pi(n_c, constant if add is not None else empty,
+                           n_out, pi, add if add is not None else empty)
+
+
+def estep_posteriors_student_t(logw: torch.Tensor, add: torch.Tensor,
+                               nu: float, d: int, s: torch.Tensor | None,
+                               n_c: torch.Tensor
+                               ) -> tuple[torch.Tensor, torch.Tensor,
+                                          torch.Tensor]:
+    """CPU engine path of a t fit: logw becomes tau in place, n_c [K] is
+    filled; returns (tau, s tau u for the M-step, likelihood)."""
+    tau, w_m, n, lik = cpu.estep_posteriors_student_t(logw, add, nu, d, s)
+    logw.copy_(tau)
+    n_c.copy_(n)
+    return logw, w_m, lik
+
+
 def estep_posteriors_weighted(logw: torch.Tensor, s: torch.Tensor
                               ) -> tuple[torch.Tensor, torch.Tensor,
                                          torch.Tensor]:

@@ -245,6 +245,109 @@ void background_update(torch::Tensor n0_part, int64_t nparts, double n_total,
   HIP_CHECK(hipGetLastError());
 }
 
+// Blocks student_t_lse launches for n events: one per tile of 4 * kNT
+// events, capped (the blocks walk further tiles in order). n_part has
+// exactly this many rows of K, lik_part this many slots.
+int64_t student_t_lse_blocks(int64_t n) { return event_weight_lse_blocks(n); }
+
+// student_t_lse over logw [K, N] in place. train: logw <- lt + ln u, lse_m,
+// lse_t, n_part [blocks, K] and (unless empty) lik_part [blocks]; s / lns
+// empty: unweighted. Posterior (train false): logw <- lt and lse_t only;
+// s, lns, lse_m, n_part and lik_part must be empty.
+void student_t_lse(torch::Tensor logw, torch::Tensor add, torch::Tensor s,
+                   torch::Tensor lns, torch::Tensor lse_m,
+                   torch::Tensor lse_t, torch::Tensor n_part,
+                   torch::Tensor lik_part, double nu, int64_t d,
+                   double delta, bool train) {
+  check_f32(logw, "logw");
+  check_f32(add, "add");
+  check_f32(s, "s");
+  check_f32(lns, "lns");
+  check_f32(lse_m, "lse_m");
+  check_f32(lse_t, "lse_t");
+  check_f32(n_part, "n_part");
+  check_f32(lik_part, "lik_part");
+  TORCH_CHECK(logw.dim() == 2 && logw.numel() >= 1, "logw must be [K, N]");
+  const int64_t k = logw.size(0);
+  const int64_t n = logw.size(1);
+  TORCH_CHECK(nu > 0.0 && std::isfinite(nu) && d >= 1 && std::isfinite(delta),
+              "student_t_lse needs finite nu > 0, D >= 1 and a finite delta");
+  // the LDS table of per-wave cluster sums: 4 rows of K floats
+  TORCH_CHECK(k <= 2048, "student_t_lse supports K <= 2048, got ", k);
+  TORCH_CHECK(add.numel() == k, "add must be [K]");
+  TORCH_CHECK(lse_t.numel() == n, "lse_t must be [N]");
+  const bool weighted = s.numel() > 0;
+  const int64_t grid = student_t_lse_blocks(n);
+  if (train) {
+    TORCH_CHECK(lse_m.numel() == n, "lse_m must be [N]");
+    TORCH_CHECK((!weighted && lns.numel() == 0) ||
+                    (s.numel() == n && lns.numel() == n),
+                "s and lns must both be empty or [N]");
+    TORCH_CHECK(n_part.numel() == grid * k,
+                "n_part must be [student_t_lse_blocks(N), K]");
+    TORCH_CHECK(lik_part.numel() == 0 || lik_part.numel() == grid,
+                "lik_part must be empty or [student_t_lse_blocks(N)]");
+  } else {
+    TORCH_CHECK(s.numel() == 0 && lns.numel() == 0 && lse_m.numel() == 0 &&
+                    n_part.numel() == 0 && lik_part.numel() == 0,
+                "posterior mode takes logw, add and lse_t only");
+  }
+  auto aligned = [](const torch::Tensor& t) {
+    return t.numel() == 0 ||
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  // n % 4 == 0 keeps every cluster row of logw 16-byte aligned
+  const int64_t nvec = (n % EW_VEC == 0 && aligned(logw) && aligned(s) &&
+                        aligned(lns) && aligned(lse_m) && aligned(lse_t))
+                           ? n / EW_VEC : 0;
+  auto ptr = [](torch::Tensor& t) {
+    return t.numel() ? t.data_ptr<float>() : (float*)nullptr;
+  };
+  const size_t lds = train ? sizeof(float) * (kNT / 64) * k : 0;
+  const float nuf = (float)nu, nud = (float)(nu + (double)d),
+              df = (float)delta;
+#define ST_LAUNCH(W, TRAIN)                                                  \
+  hipLaunchKernelGGL((gmm::student_t_lse_kernel<W, TRAIN>),                  \
+                     dim3((unsigned)grid), dim3(kNT), lds, stream(),         \
+                     logw.data_ptr<float>(), add.data_ptr<float>(), ptr(s),  \
+                     ptr(lns), ptr(lse_m), lse_t.data_ptr<float>(),          \
+                     ptr(n_part), ptr(lik_part), (int)k, nvec, n, nuf, nud,  \
+                     df)
+  if (!train) {
+    ST_LAUNCH(false, false);
+  } else if (weighted) {
+    ST_LAUNCH(true, true);
+  } else {
+    ST_LAUNCH(false, true);
+  }
+#undef ST_LAUNCH
+  HIP_CHECK(hipGetLastError());
+}
+
+// N and pi (and add = constant + ln pi unless `add` is empty) of a t fit
+// from the reduced responsibilities n_c [K].
+void student_t_pi(torch::Tensor n_c, torch::Tensor constant,
+                  torch::Tensor n_out, torch::Tensor pi, torch::Tensor add) {
+  check_f32(n_c, "n_c");
+  check_f32(constant, "constant");
+  check_f32(n_out, "n_out");
+  check_f32(pi, "pi");
+  check_f32(add, "add");
+  const int64_t k = n_c.numel();
+  TORCH_CHECK(k >= 1 && n_out.numel() == k && pi.numel() == k,
+              "n_c, N and pi must be [K]");
+  TORCH_CHECK(add.numel() == 0 || (add.numel() == k && constant.numel() == k),
+              "add must be empty or [K] with constant [K]");
+  hipLaunchKernelGGL(gmm::student_t_pi_kernel, dim3(1), dim3(kNT), 0,
+                     stream(), n_c.data_ptr<float>(),
+                     add.numel() ? constant.data_ptr<float>()
+                                 : (const float*)nullptr,
+                     n_out.data_ptr<float>(), pi.data_ptr<float>(),
+                     add.numel() ? add.data_ptr<float>() : (float*)nullptr,
+                     (int)k);
+  HIP_CHECK(hipGetLastError());
+}
+
 template <typename T>
 void mstep_cov_impl(const torch::Tensor& x, const torch::Tensor& w,
                     const torch::Tensor& lse, torch::Tensor& partials) {
@@ -1119,6 +1222,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "block partials of n0 and (optionally) the likelihood");
   m.def("background_update", &background_update,
         "background state (pi0, b, lik_add, n0) from the n0 partials");
+  m.def("student_t_lse", &student_t_lse,
+        "Student-t components on the lse contract: logw [K, N] in place, "
+        "lse_t, and in train mode lse_m plus block partials of N_c and the "
+        "likelihood");
+  m.def("student_t_lse_blocks", &student_t_lse_blocks,
+        "block (= partial row) count of student_t_lse for N events");
+  m.def("student_t_pi", &student_t_pi,
+        "N, pi (and add) of a t fit from the reduced responsibilities");
   m.def("mstep_covariance_partials", &mstep_covariance_partials,
         "packed weighted second-moment partials [nchunk,K,P]");
   m.def("constants", &constants,

@@ -430,6 +430,235 @@ background_update_kernel(const float* __restrict__ n0_part, int64_t nparts,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Student-t mixture components (fixed degrees of freedom nu) on the lse
+// contract: one pass over the Gaussian log-weights logw[c*n + e] =
+// add_c - q/2 an lse-family E-step left, rewriting what the M-step reads.
+// Per (cluster, event), with h = (nu + D) / 2 and delta(nu, D) the constant
+// that turns the Gaussian normaliser into the t one:
+//   q    = max(0, 2 (add_c - logw))             squared Mahalanobis distance
+//   lt   = (add_c + delta) - h log1p(q / nu)    ln(pi_c t_c(x_e))
+//   u    = (nu + D) / (nu + q)                  the latent scale's mean
+// and per event lse_t = logsumexp_c lt by an online (max, sum) recurrence.
+// TRAIN: logw <- lt + ln u, so exp(logw - lse_m) is s tau u, the weight of
+//   the parameter-expanded M-step; lse_m = lse_t, or with weights (W)
+//   lse_t - lns and +inf where s == 0 (bitwise event_weight_lse_kernel on
+//   lse_t); lse_t itself is stored too. Block partials, written by every
+//   launched block: n_part[blockIdx.x * k + c] = sum_e s_e exp(lt - lse_t)
+//   (the true responsibilities: pi and N come from them, not from the
+//   moments' corner) and, when lik_part is non-null, lik_part[blockIdx.x] =
+//   sum_e s_e lse_t (zero-weight events skipped, not multiplied).
+// !TRAIN (posterior): logw <- lt, lse_t stored, nothing else written.
+// q = +inf gives lt = -inf and weight 0; an event whose lt are all -inf has
+// lse_t = -inf and contributes exact zeros to n_part, never NaN.
+//
+// Geometry: a block walks tiles of NT * V events (tile = blockIdx.x,
+// += gridDim.x), V = 4 events per thread as one 16-byte access over the
+// first nvec * 4 events (the launcher passes nvec = 0 unless every pointer
+// is 16-byte aligned and n % 4 == 0, which keeps every cluster row aligned)
+// and V = 1 over the rest. Posterior mode sweeps a thread's column of logw
+// once, storing lt as it goes. Train mode sweeps it twice per tile: once for
+// lse_t (kept in registers with s), once to rewrite logw and sum
+// exp(lt - lse_t), which needs the finished lse_t (lt + ln u alone would not
+// let the second sweep recover lt); the tile's 1024 K floats were just
+// read, so the second read is served by whatever cache still holds them. The
+// per-cluster sums go wave-reduce -> this wave's row of the LDS table
+// [NT / WAVE][k] (only that wave ever touches its row, tiles in order) ->
+// one combine in wave order at the end: fixed event sets, fixed order, no
+// float atomics. The accurate expf / logf / log1pf, as in background_lse:
+// h log1p(q / nu) is the whole tail behaviour.
+// ---------------------------------------------------------------------------
+template <int V>
+__device__ __forceinline__ void st_load(const float* p, float* o) {
+  if constexpr (V == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o[u] = v[u];
+  } else {
+    o[0] = p[0];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void st_store(float* p, const float* o) {
+  if constexpr (V == 4) {
+    f32x4 v;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = o[u];
+    *reinterpret_cast<f32x4*>(p) = v;
+  } else {
+    p[0] = o[0];
+  }
+}
+
+// One tile: this thread's V events start at e0 (`active` false past the
+// end: the thread still takes part in the wave sums, adding zeros).
+template <int V, bool W, bool TRAIN>
+__device__ __forceinline__ void student_t_tile(
+    float* __restrict__ logw, const float* __restrict__ add,
+    const float* __restrict__ s, const float* __restrict__ lns,
+    float* __restrict__ lse_m, float* __restrict__ lse_t, int k, int64_t n,
+    int64_t e0, bool active, float nu, float nud, float delta,
+    float* __restrict__ tab_row, float* lik) {
+  const float h = 0.5f * nud;
+  float lt_lse[V], sv[V];
+#pragma unroll
+  for (int u = 0; u < V; ++u) {
+    lt_lse[u] = -INFINITY;
+    sv[u] = 1.0f;
+  }
+  if (active) {
+    float m[V], sum[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      m[u] = -INFINITY;
+      sum[u] = 0.0f;
+    }
+    for (int c = 0; c < k; ++c) {
+      const float ac = add[c];
+      const float a = ac + delta;
+      float lw[V];
+      st_load<V>(logw + (int64_t)c * n + e0, lw);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        const float q = fmaxf(0.0f, 2.0f * (ac - lw[u]));
+        const float lt = a - h * log1pf(q / nu);
+        if (lt > m[u]) {
+          // m == -inf: expf(-inf) = 0 and the sum restarts at 1
+          sum[u] = sum[u] * expf(m[u] - lt) + 1.0f;
+          m[u] = lt;
+        } else if (lt != -INFINITY) {
+          sum[u] += expf(lt - m[u]);
+        }
+        lw[u] = lt;
+      }
+      // posterior mode is done with this column after one sweep: lt does
+      // not depend on lse_t
+      if (!TRAIN) st_store<V>(logw + (int64_t)c * n + e0, lw);
+    }
+#pragma unroll
+    for (int u = 0; u < V; ++u)
+      lt_lse[u] = m[u] == -INFINITY ? -INFINITY : m[u] + logf(sum[u]);
+    st_store<V>(lse_t + e0, lt_lse);
+    if (TRAIN) {
+      float lm[V];
+      if (W) {
+        float ls[V];
+        st_load<V>(s + e0, sv);
+        st_load<V>(lns + e0, ls);
+#pragma unroll
+        for (int u = 0; u < V; ++u)
+          lm[u] = event_weight_one(lt_lse[u], sv[u], ls[u], lik);
+      } else {
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          lm[u] = lt_lse[u];
+          *lik += lt_lse[u];
+        }
+      }
+      st_store<V>(lse_m + e0, lm);
+    }
+  }
+  if (!TRAIN) return;
+  // second sweep (train): rewrite logw, per-cluster sums of the
+  // responsibilities exp(lt - lse_t), which need the finished lse_t
+  for (int c = 0; c < k; ++c) {
+    float acc = 0.0f;
+    if (active) {
+      const float ac = add[c];
+      const float a = ac + delta;
+      float lw[V];
+      st_load<V>(logw + (int64_t)c * n + e0, lw);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        const float q = fmaxf(0.0f, 2.0f * (ac - lw[u]));
+        const float lt = a - h * log1pf(q / nu);
+        lw[u] = lt + logf(nud / (nu + q));
+        if (lt != -INFINITY && !(W && sv[u] == 0.0f)) {
+          const float tau = expf(lt - lt_lse[u]);
+          acc += W ? sv[u] * tau : tau;
+        }
+      }
+      st_store<V>(logw + (int64_t)c * n + e0, lw);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+      acc += __shfl_down(acc, off, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) tab_row[c] += acc;
+  }
+}
+
+template <bool W, bool TRAIN>
+__global__ void __launch_bounds__(NT)
+student_t_lse_kernel(float* __restrict__ logw, const float* __restrict__ add,
+                     const float* __restrict__ s,
+                     const float* __restrict__ lns,
+                     float* __restrict__ lse_m, float* __restrict__ lse_t,
+                     float* __restrict__ n_part,
+                     float* __restrict__ lik_part, int k, int64_t nvec,
+                     int64_t n, float nu, float nud, float delta) {
+  extern __shared__ float st_tab[];  // TRAIN: [NT / WAVE][k]
+  float* tab_row = st_tab + (size_t)(threadIdx.x / WAVE) * k;
+  if (TRAIN) {
+    for (int c = threadIdx.x; c < (NT / WAVE) * k; c += NT) st_tab[c] = 0.0f;
+    __syncthreads();
+  }
+  float lik = 0.0f;
+  const int64_t vtiles = (nvec + NT - 1) / NT;
+  for (int64_t t = blockIdx.x; t < vtiles; t += gridDim.x) {
+    const int64_t v = t * NT + threadIdx.x;
+    student_t_tile<EW_VEC, W, TRAIN>(logw, add, s, lns, lse_m, lse_t, k, n,
+                                     v * EW_VEC, v < nvec, nu, nud, delta,
+                                     tab_row, &lik);
+  }
+  const int64_t tail0 = nvec * EW_VEC;
+  const int64_t ttiles = (n - tail0 + NT - 1) / NT;
+  for (int64_t t = blockIdx.x; t < ttiles; t += gridDim.x) {
+    const int64_t e = tail0 + t * NT + threadIdx.x;
+    student_t_tile<1, W, TRAIN>(logw, add, s, lns, lse_m, lse_t, k, n, e,
+                                e < n, nu, nud, delta, tab_row, &lik);
+  }
+  if (TRAIN) {
+    __syncthreads();
+    for (int c = threadIdx.x; c < k; c += NT) {
+      float total = 0.0f;
+      for (int wv = 0; wv < NT / WAVE; ++wv) total += st_tab[wv * k + c];
+      n_part[(int64_t)blockIdx.x * k + c] = total;
+    }
+    if (lik_part != nullptr) {  // kernel argument: uniform over the block
+      __shared__ float wsum[NT / WAVE];
+      block_sum(lik, wsum, lik_part);
+    }
+  }
+}
+
+// One block, after finalize: the mixing weights and counts of a t fit from
+// the reduced responsibilities n_c = sum_e s_e tau_ce (finalize derived its
+// own from the moments' corner, which holds sum s tau u):
+//   N[c] = n_c,  pi[c] = n_c < 0.5 ? 1e-10 : n_c / sum_c n_c
+// with the sum taken in cluster order by one fp32 accumulator, as finalize
+// does; add[c] = constant[c] + logf(pi[c]) when `add` is non-null.
+__global__ void __launch_bounds__(NT)
+student_t_pi_kernel(const float* __restrict__ n_c,
+                    const float* __restrict__ constant,
+                    float* __restrict__ n_out, float* __restrict__ pi,
+                    float* __restrict__ add, int k) {
+  __shared__ float total_sh;
+  if (threadIdx.x == 0) {
+    float total = 0.0f;
+    for (int c = 0; c < k; ++c) total += n_c[c];
+    total_sh = total;
+  }
+  __syncthreads();
+  const float total = total_sh;
+  for (int c = threadIdx.x; c < k; c += NT) {
+    const float nc = n_c[c];
+    const float p = nc < 0.5f ? 1e-10f : nc / total;
+    n_out[c] = nc;
+    pi[c] = p;
+    if (add != nullptr) add[c] = constant[c] + logf(p);
+  }
+}
+
 // Deterministic chunk reduction: out[j] = sum_i in[i*m + j] (fixed i
 // order). Replaces torch's generic reduce_kernel (19.6 us for the
 // [256, K*Pp] moments partials).

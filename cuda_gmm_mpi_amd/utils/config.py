@@ -101,6 +101,13 @@ class GmmConfig:
     background_warmup: int = 5
     background_log_volume: float | None = None
 
+    # Student-t mixture components with this many degrees of freedom (fixed,
+    # not estimated); 0 = Gaussian components. Events in a population's tail
+    # are down-weighted by u = (nu + D) / (nu + q) instead of inflating its
+    # covariance. R is then the t scale matrix: the covariance is
+    # nu / (nu - 2) * R for nu > 2.
+    student_t_nu: float = 0.0
+
     def validate(self) -> None:
         if not (1 <= self.num_clusters <= MAX_CLUSTERS):
             raise ValueError(
@@ -145,6 +152,23 @@ class GmmConfig:
             raise ValueError(
                 "background cannot be combined with checkpoint_dir (the "
                 "checkpoint does not hold the background's state)")
+
+        if (isinstance(self.student_t_nu, bool)
+                or not isinstance(self.student_t_nu, (int, float))
+                or not math.isfinite(float(self.student_t_nu))
+                or float(self.student_t_nu) < 0.0):
+            raise ValueError("student_t_nu must be finite and >= 0 "
+                             f"(0 = Gaussian components): "
+                             f"{self.student_t_nu!r}")
+        if self.student_t_nu > 0 and self.background:
+            raise ValueError(
+                "student_t_nu cannot be combined with background (the "
+                "background pass and the t pass both rewrite the lse the "
+                "M-step reads; combining them is not implemented)")
+        if self.student_t_nu > 0 and self.checkpoint_dir:
+            raise ValueError(
+                "student_t_nu cannot be combined with checkpoint_dir (a "
+                "checkpoint does not record the degrees of freedom)")
 
     @property
     def stop_number(self) -> int:

@@ -123,7 +123,8 @@ def format_cluster_block(c: int, pi: float, n: float, means: np.ndarray,
 
 
 def write_summary(path: str, state, enable_output: bool = True,
-                  background: dict | None = None) -> None:
+                  background: dict | None = None,
+                  student_t_nu: float = 0.0) -> None:
     """Writes <out>.summary (gaussian.cu:1015-1040).
 
     The file is always created; cluster blocks are written only when output
@@ -133,6 +134,10 @@ def write_summary(path: str, state, enable_output: bool = True,
     a fit that has one: the cluster Probability lines then hold the mixture
     weights (1 - pi0) * pi_c, and a trailing "Background" block its
     Probability, N and Log volume as %f.
+
+    ``student_t_nu`` > 0 marks a fit with Student-t components: a trailing
+    "Student-t" block holds the degrees of freedom (%r, so it reads back
+    exactly); the R matrices are then scale matrices.
     """
     scale = 1.0 - float(background["pi"]) if background else 1.0
     with open(path, "w") as f:
@@ -152,6 +157,10 @@ def write_summary(path: str, state, enable_output: bool = True,
                         f"N: {float(background['n']):f}\n"
                         f"Log volume: {float(background['log_volume']):f}\n"
                         "\n\n")
+            if student_t_nu and float(student_t_nu) > 0.0:
+                f.write("Student-t\n"
+                        f"Degrees of freedom: {float(student_t_nu)!r}\n"
+                        "\n\n")
 
 
 def read_summary(path: str) -> dict[str, np.ndarray]:
@@ -161,23 +170,29 @@ def read_summary(path: str) -> dict[str, np.ndarray]:
     are rounded to that. A trailing "Background" block (write_summary)
     adds background_pi, background_n and background_log_volume as float64
     scalars; the pi of such a file are mixture weights (1 - pi0) * pi_c.
+    A trailing "Student-t" block adds student_t_nu (float64).
     Raises ValueError on anything else."""
     with open(path, "r") as f:
         lines = [ln.strip() for ln in f]
     pi, n, means, rs = [], [], [], []
-    background = {}
+    extra = {}      # the trailing Background / Student-t blocks
     i = 0
     try:
         while i < len(lines):
-            if lines[i] == "Background" and not background:
-                background = {
+            if lines[i] == "Background" and "background_pi" not in extra:
+                extra.update({
                     "background_pi": np.float64(
                         lines[i + 1].split("Probability:")[1]),
                     "background_n": np.float64(lines[i + 2].split("N:")[1]),
                     "background_log_volume": np.float64(
                         lines[i + 3].split("Log volume:")[1]),
-                }
+                })
                 i += 4
+                continue
+            if lines[i] == "Student-t" and "student_t_nu" not in extra:
+                extra["student_t_nu"] = np.float64(
+                    lines[i + 1].split("Degrees of freedom:")[1])
+                i += 2
                 continue
             if not lines[i].startswith("Cluster #"):
                 if lines[i]:
@@ -208,7 +223,7 @@ def read_summary(path: str) -> dict[str, np.ndarray]:
         "N": np.asarray(n, dtype=np.float32),
         "means": np.asarray(means, dtype=np.float32),
         "R": np.asarray(rs, dtype=np.float32),
-        **background,
+        **extra,
     }
 
 
